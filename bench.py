@@ -9,16 +9,19 @@ trust region 0.25 (:207), 8 static spherical obstacles as linearized soft halfsp
 One SCvx iteration (= one "step") = batched FOH discretization (scvx_foh_batched) + batched
 trust-region QP/SOCP solve to tolerance (scvx_qp_solve_batched) + trust-region bookkeeping, all
 on device; inputs resident in HBM.  The headline `value` runs the reference's outer rule
-(dist_scvx_3d.py:248-252: one trust radius, halved when the summed cost rises); the same invocation
-then times this build's per-agent rule (each agent's radius halves on its own cost increase) from the
-same initial iterate, with its own warmup, reported under `other_rule` (`--rules one` skips it).
+(dist_scvx_3d.py:248-252: one trust radius, halved when the summed cost rises).  A plain run sets up, warms
+up, times the steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the result
+line.  With --full the same invocation then times this build's per-agent rule (each agent's radius halves
+on its own cost increase) from the same initial iterate, with its own warmup, reported under `other_rule`
+(`--rules one` skips it).
 Multi-GPU (--gpus N under torch.distributed.run): weak scaling, each rank owns its own 1024 agents; the
 only exchange is the global rule's summed cost (one scalar all_reduce per step, RCCL); `value` counts
 the N_gpus * 1024-agent SCvx iterations completed per second.
 
 Also reported: roofline of the dominant kernel (qp_ipm_kernel, FP64 FLOP rate vs the FP64 peak,
-timed with HIP events on the launch stream) and a CPU baseline (the C++ restatement of the same
-algorithm, oracle/scvx_cpu.cpp + oracle/foh_ref.c, on a bounded agent sample, the headline's rule).
+timed with HIP events on the launch stream, from the timed steps themselves) and, with --full, a CPU
+baseline (the C++ restatement of the same algorithm, oracle/scvx_cpu.cpp + oracle/foh_ref.c, on a bounded
+agent sample, the headline's rule).
 
 Optional workloads (--config; the default c3 is the headline line the driver records):
   c2  BASELINE.json configs[1]: N=128 double-integrator agents per GPU (seed 0, no
@@ -147,6 +150,30 @@ def shard_tensors(sc, idx, device):
     import torch
     return {k: torch.tensor(np.ascontiguousarray(sc[k][idx]), device=device)
             for k in ("X", "U", "x_init", "x_final", "sigma")}
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy in float64 (float32 arrays stay float32; integer arrays are
+    converted).  At most DUMP_MAX_BYTES in all: a larger set keeps, of every array with more than one row, the same
+    fixed seeded sample of its leading (agent) dimension."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        host[name] = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        rng = np.random.default_rng(0)
+        keep = 0.98 * DUMP_MAX_BYTES / total
+        for name, a in host.items():
+            if a.ndim and a.shape[0] > 1:
+                rows = np.sort(rng.choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+                host[name] = np.ascontiguousarray(a[rows])
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def host_info():
@@ -618,13 +645,23 @@ def timed_leg(drv, w, args, world, device):
         per_rank = [r.tolist() for r in allr]
     else:
         per_rank = None
+    last = None
+    if args.steps > 0:
+        # what the last timed step returned to its caller (--dump-outputs): the new iterate, the raw solver outputs
+        # the subproblem wrote (the collision slack / virtual control only where the template has them) and the radii
+        last = {"X": it_state[0], "U": it_state[1], "tr": drv.tr, "qp_X": out["X"], "qp_U": out["U"],
+                "qp_obj": out["obj"], "qp_status": out["status"], "qp_iters": out["iters"]}
+        if drv.spec.j_max:
+            last["qp_slack_coll"] = out["slack_coll"]
+        if getattr(drv.spec, "w_nu", 0):
+            last["qp_nu"] = out["nu"]
     h = hist[:args.steps].cpu().numpy()   # (steps, 2, N): IPM iterations, status
     its, status = h[-1, 0], h[-1, 1]
     N = its.size
     stats = [[int((h[i, 1] == k).sum()) for k in (0, 1, 2)] for i in range(args.steps)]
     return dict(
         el=el_t.item(), st_ms=st_ms, step_ms=step_ms, per_rank=per_rank, host_ms=host_ms, checks=checks,
-        ipm_iters=float(h[:, 0].sum()),
+        ipm_iters=float(h[:, 0].sum()), last=last,
         fields={
             "ms_per_step_median": float(np.median(step_ms)),
             "stage_ms_median": st_ms,
@@ -676,7 +713,14 @@ def main():
     ap.add_argument("--config", choices=("c2", "c3", "c4", "c5", "is", "scp", "nash"), default="c3")
     ap.add_argument("--agents", type=int, default=None, help="c2 / c3: agents per GPU (default 128 / 1024)")
     ap.add_argument("--cpu-sample", type=int, default=1024)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline line, also measure what a plain run leaves out: the CPU baseline "
+                         "(`cpu_baseline`, unless --no-cpu) and, for c2/c3, the other trust-region rule (`other_rule`, "
+                         "unless --rules one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2-c5: after the timed steps write what the last timed step returned (the new iterate X, U, "
+                         "the radii tr and the solver outputs qp_*) as DIR/<name>.npy (rank 0's agents at --gpus > 1)")
     ap.add_argument("--balance", action="store_true",
                     help="c4/c5 at --gpus > 1: deal agents to ranks by their first-step IPM iterations (DESIGN §6)")
     ap.add_argument("--tol", type=float, default=1e-8,
@@ -690,9 +734,10 @@ def main():
                          "when the summed cost rises: Distributed_opt/dist_scvx_3d.py:248-252; at --gpus > 1 the sum "
                          "is all-reduced over every rank's agents) or per_agent (each agent's radius halves on its "
                          "own cost increase: this build's extension for independent agents)")
-    ap.add_argument("--rules", default="both", choices=("both", "one"),
-                    help="c2/c3: both -- also time the other trust-region rule in the same invocation (its own "
-                         "warmup and timed steps, reported under `other_rule`); one -- only --tr-rule")
+    ap.add_argument("--rules", default=None, choices=("both", "one"),
+                    help="c2/c3: both (the default with --full) -- also time the other trust-region rule in the same "
+                         "invocation (its own warmup and timed steps, reported under `other_rule`); one (the default "
+                         "without --full) -- only --tr-rule")
     ap.add_argument("--tie-rtol", type=float, default=1e-9,
                     help="per-agent trust-region rule: relative margin of the cost-increase test (JacobiSCvx.tie_rtol)")
     ap.add_argument("--dispatch-order", default="lpt", choices=("lpt", "none"),
@@ -706,6 +751,11 @@ def main():
     args = ap.parse_args()
     if args.agents is None:
         args.agents = 128 if args.config == "c2" else N_AGENTS
+    if args.rules is None:
+        args.rules = "both" if args.full else "one"
+    args.no_cpu = args.no_cpu or not args.full   # the CPU baselines are part of --full only
+    if args.dump_outputs and (args.config not in ("c2", "c3", "c4", "c5") or args.steps < 1):
+        raise SystemExit("bench.py: --dump-outputs needs --config c2/c3/c4/c5 and --steps >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -778,6 +828,8 @@ def main():
     rows = qp_rows(n, m, len(box), n_obs, j_max, soc)
     nsub = drv.nsub   # the FOH substeps the timed loop ran (scvx_hip.default_nsub for its interval)
     res = timed_leg(drv, w, args, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res["last"])
     roof, step_roof = leg_roofline(res, args, n, m, K, N, rows, j_max, model, nsub)
     primary_cfg = dict(tr_rule=drv.tr_rule, qp_dispatch="longest-first (last-step IPM iterations)"
                        if getattr(drv, "_lpt", False) else "agent order")

@@ -50,6 +50,33 @@ def test_world_size_mismatch_is_refused():
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
 
 
+def test_full_option_is_accepted():
+    line = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--dry-run")
+    assert line["n_gpus"] == 1 and line["steps"] == 2
+
+
+def test_dump_outputs_writes_float_arrays_within_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs: one .npy per name, integer arrays as float64, float32 kept; over the byte cap every
+    many-row array keeps the same seeded sample of rows, identical from call to call."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"X": rng.normal(size=(40, 5, 6)), "iters": np.arange(40, dtype=np.int32),
+              "h": rng.normal(size=(40, 3)).astype(np.float32), "tr": np.array([0.25])}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert got["X"].dtype == np.float64 and got["iters"].dtype == np.float64 and got["h"].dtype == np.float32
+    assert all(np.array_equal(got[k], arrays[k]) for k in arrays)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    small = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in arrays}
+    assert sum(a.nbytes for a in small.values()) <= 4000
+    assert 1 <= small["X"].shape[0] < 40 and small["X"].shape[1:] == (5, 6) and small["tr"].shape == (1,)
+    assert all(np.array_equal(small[k], np.load(tmp_path / "c" / f"{k}.npy")) for k in arrays)
+
+
 def test_algorithmic_counts_c3():
     sys.path.insert(0, REPO)
     import bench

@@ -15,7 +15,7 @@ if [ "$TESTS" != none ]; then
 fi
 [ "$CONFIGS" = none ] && CONFIGS=""
 for c in $CONFIGS; do
-  if [ "${CPU:-0}" = 1 ] && [ $c = c3 ]; then X=""; else X="--no-cpu"; fi
+  if [ "${CPU:-0}" = 1 ] && [ $c = c3 ]; then X="--full"; else X="--no-cpu"; fi
   timeout -k 10 300 python -u bench.py --config $c $X > gpurun_out/bench_${c}_$TAG.log 2>&1
   python -c "
 import json; l=[x for x in open('gpurun_out/bench_${c}_$TAG.log') if x.startswith('{')][-1]; d=json.loads(l); print('$c', round(d['value'],2), round(d['ms_per_step_median'],4), d.get('ipm_iters_per_agent'), d.get('ipm_iters_max_per_step', [])[:10], d.get('status_counts'), d.get('status_counts_per_step'))"

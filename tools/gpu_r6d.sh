@@ -9,7 +9,8 @@ T=${1:-r6d}
 timeout -k 10 700 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu_$T.log 2>&1 || { rc=$?; echo "pytest rc $rc"; [ $rc -eq 1 ] || exit $rc; }
 tail -n 2 gpurun_out/pytest_gpu_$T.log
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$T.log 2>&1
-timeout -k 10 300 python -u bench.py > gpurun_out/bench_c3_$T.log 2>&1
+OUT=${OUT:-bench_logs}; mkdir -p $OUT
+timeout -k 10 300 python -u bench.py --full > $OUT/bench_c3_$T.log 2>&1
 timeout -k 10 300 python -u bench.py --config c4 --no-cpu > gpurun_out/bench_c4_$T.log 2>&1
 timeout -k 10 300 python -u bench.py --config c5 --no-cpu > gpurun_out/bench_c5_$T.log 2>&1
 SCVX_HIP_LIB=variants/focc2/libscvx_hip.so timeout -k 10 300 python -u bench.py --config c5 --no-cpu > gpurun_out/bench_c5_focc2_$T.log 2>&1
