@@ -3,6 +3,8 @@
 // instantiation (qp_inst_*.hip).
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "common.hpp"
 #include "qp_caps.hpp"
 #include "qp_ipm.hpp"
@@ -14,6 +16,11 @@ int qp_launch_di(int idx, const QPArgs& a, hipStream_t st);
 int qp_launch_unicycle(int idx, const QPArgs& a, hipStream_t st);
 int qp_launch_si(int idx, const QPArgs& a, hipStream_t st);
 int qp_launch_quad(int idx, const QPArgs& a, hipStream_t st);
+// SCVX_QP_GENERIC_K (qp_inst.hpp): the runtime-K instantiation also where a K-specialised one exists
+bool qp_force_generic_k() {
+    const char* e = std::getenv("SCVX_QP_GENERIC_K");
+    return e && e[0] && !(e[0] == '0' && !e[1]);
+}
 }  // namespace scvx
 
 using namespace scvx;

@@ -105,14 +105,31 @@ constexpr int qp_ncol(int nx, int nu, int nb, int ns, int ng, int nv = 0) {
 }
 // factor outputs per stage (stage-major block): K, kappa, LD, W2, P, Pi, u, Acl, [virtual control: G^-1 P,
 // G^-1 Pi, G^-1, Acl~], [stiff facets: Gamma, Gamma_kappa, W, C^-1, facet indices], one junk slot (the global
-// store of lanes without an output of their own)
+// store of lanes without an output of their own).  Every sub-block starts on an even element (one padding double
+// after a sub-block of odd size; the small block W | C^-1 | indices stays contiguous) and the block size is even:
+// with the 16-byte region bases of qp_ws_doubles the lane-parallel passes read a sub-block two doubles per load
+// (QPCfg::B_* is the same chain of qp_even; C3: 178 -> 180 doubles)
 constexpr int qp_fbs(int nx, int nu, int nv = 0, int nc = 0) {
-    return 3 * nu * nx + nu * nu + 3 * nx * nx + nx + 4 * nv * nx +
-           qp_pm(nx, nu, nc) * (2 * nx + nu + qp_pm(nx, nu, nc) + 1) + 1;
+    const int pm = qp_pm(nx, nu, nc);
+    int o = 0;
+    o = qp_even(o + nu * nx);   // K
+    o = qp_even(o + nu * nx);   // kappa
+    o = qp_even(o + nu * nu);   // LD
+    o = qp_even(o + nu * nx);   // W2
+    o = qp_even(o + nx * nx);   // P
+    o = qp_even(o + nx * nx);   // Pi
+    o = qp_even(o + nx);        // u
+    o = qp_even(o + nx * nx);   // Acl
+    for (int i = 0; i < 4; ++i) o = qp_even(o + nv * nx);   // G^-1 P, G^-1 Pi, G^-1, Acl~
+    o = qp_even(o + pm * nx);   // Gamma
+    o = qp_even(o + pm * nx);   // Gamma_kappa
+    o = o + nu * pm + pm * pm + pm;   // W | C^-1 | indices: one contiguous small block
+    return qp_even(o + 1);      // junk slot
 }
-// per agent: columns [c][K], packets [K][GPK], factor blocks [K][FBS] -- only the K nodes: lanes >= K
+// per agent: columns [c][K], packets [K][GPK], factor blocks [K][FBS], each region from a 16-byte boundary (the
+// column and the packet region rounded up to an even number of doubles: odd K) -- only the K nodes: lanes >= K
 // address past the end of the buffer (loads read 0, stores are dropped), so the agent's footprint is
-// what its nodes touch (C3: 1024 agents x 199 KB stay inside the 256 MB Infinity Cache)
+// what its nodes touch (C3: 1024 agents x 233 KB stay inside the 256 MB Infinity Cache)
 // n = 12 classes: the factor's per-lane phase descriptors, [repetition][lane] x 16 bytes (QPRepC + pad), after the
 // factor blocks (agent-independent, rewritten at each sweep; see the factor sweep)
 constexpr int qp_nrep(int nx, int nu) {
@@ -120,8 +137,8 @@ constexpr int qp_nrep(int nx, int nu) {
 }
 constexpr int qp_dtab(int nx, int nu) { return nx > 8 ? qp_nrep(nx, nu) * 64 * 2 : 0; }
 constexpr long long qp_ws_doubles(int nx, int nu, int nb, int ns, int ng, int K, int nv = 0, int nc = 0) {
-    return (long long)K * (qp_ncol(nx, nu, nb, ns, ng, nv) + qp_gpk(nx, nu, nv, nc) + qp_fbs(nx, nu, nv, nc)) +
-           qp_dtab(nx, nu);
+    return (long long)qp_even(K * qp_ncol(nx, nu, nb, ns, ng, nv)) + qp_even(K * qp_gpk(nx, nu, nv, nc)) +
+           (long long)K * qp_fbs(nx, nu, nv, nc) + qp_dtab(nx, nu);
 }
 // LDS doubles of a class (QPCfg::lds_doubles, written out for the host of a runtime-compiled class, which
 // has no QPCfg instantiation; QPCfg asserts that both agree)
@@ -248,26 +265,27 @@ struct QPCfg {
     // factor outputs: stage-major blocks [t][FBS] (coalesced stores from the element-parallel
     // factor; each lane-parallel pass reads its own stage's block)
     static constexpr int B_K = 0;                  // K      NU x NX
-    static constexpr int B_KAP = B_K + NU * NX;    // kappa  NU x NX
-    static constexpr int B_LD = B_KAP + NU * NX;   // LDL' of Rhat: L[i][j] (i > j), 1/d_i on the diagonal
-    static constexpr int B_W2 = B_LD + NU * NU;    // W2 = Bt' Pi_{t+1}  NU x NX
-    static constexpr int B_P = B_W2 + NU * NX;     // P_t
-    static constexpr int B_PI = B_P + NX * NX;     // Pi_t
-    static constexpr int B_U = B_PI + NX * NX;     // P_{t+1} e_t
-    static constexpr int B_ACL = B_U + NX;         // Acl_t = A_t + Bt_t K_t (row-major)
+    // (every sub-block on an even element, padded where the one before has an odd size: 16-byte loads, ldb)
+    static constexpr int B_KAP = qp_even(B_K + NU * NX);    // kappa  NU x NX
+    static constexpr int B_LD = qp_even(B_KAP + NU * NX);   // LDL' of Rhat: L[i][j] (i > j), 1/d_i on the diagonal
+    static constexpr int B_W2 = qp_even(B_LD + NU * NU);    // W2 = Bt' Pi_{t+1}  NU x NX
+    static constexpr int B_P = qp_even(B_W2 + NU * NX);     // P_t
+    static constexpr int B_PI = qp_even(B_P + NX * NX);     // Pi_t
+    static constexpr int B_U = qp_even(B_PI + NX * NX);     // P_{t+1} e_t
+    static constexpr int B_ACL = qp_even(B_U + NX);         // Acl_t = A_t + Bt_t K_t (row-major)
     // virtual control (VC): G^-1 P_{t+1}, G^-1 Pi_{t+1}, G^-1 (column-major), the chain matrix
     // Acl~ = G^-1 D Acl (row-major)
-    static constexpr int B_YP = B_ACL + NX * NX, B_YPI = B_YP + NV * NX, B_GI = B_YPI + NV * NX,
-                         B_ACL2 = B_GI + NV * NX;
+    static constexpr int B_YP = qp_even(B_ACL + NX * NX), B_YPI = qp_even(B_YP + NV * NX),
+                         B_GI = qp_even(B_YPI + NV * NX), B_ACL2 = qp_even(B_GI + NV * NX);
     static constexpr int B_CH = NV > 0 ? B_ACL2 : B_ACL;  // what the solve chains read
     // stiff facets (STF): Gamma = -C^-1 G' R0^-1 Sh and Gamma_kappa = -C^-1 G' R0^-1 W2 (PM x NX, row-major: the
     // multiplier steps nu = Gamma xi + Gamma_kappa mu + gamma0), then W = R0^-1 G (NU x PM), C^-1 (PM x PM) and the
     // stiff facets' indices (PM, -1 = empty slot)
-    static constexpr int B_GAM = B_ACL2 + NV * NX, B_GAK = B_GAM + PM * NX, B_WS = B_GAK + PM * NX,
-                         B_CI = B_WS + NU * PM, B_SF = B_CI + PM * PM;
+    static constexpr int B_GAM = qp_even(B_ACL2 + NV * NX), B_GAK = qp_even(B_GAM + PM * NX),
+                         B_WS = qp_even(B_GAK + PM * NX), B_CI = B_WS + NU * PM, B_SF = B_CI + PM * PM;
     static constexpr int NSMB = NU * PM + PM * PM + PM;   // W | C^-1 | indices: one small block
     static constexpr int B_JNK = B_SF + PM;  // junk slot (stores of lanes without an output)
-    static constexpr int FBS = B_JNK + 1;
+    static constexpr int FBS = qp_even(B_JNK + 1);
     static_assert(FBS == qp_fbs(NX, NU, NV, NC), "factor block");
     // stage-minor workspace columns
     static constexpr int C_DT = 0;                 // disc, transposed: A (col-major) | B | C | S | z
@@ -371,6 +389,32 @@ struct QPBuf {
         soff = __builtin_amdgcn_readfirstlane(soff);
         cnt(voff, soff, 16.0);
         __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, soff, 0);
+    }
+    // A byte offset known at compile time (the K-specialised instantiations: qp_ipm_kernel's KC) is split: its low
+    // 12 bits join voffset, where the backend folds a constant addend into the instruction's immediate field, and
+    // the 4 KB window above them is the soffset -- one scalar constant shared by every access of the window, no
+    // scalar arithmetic per access.  `coff` is the whole constant part of the address (a constant added to `voff`
+    // by the caller would overflow the immediate field and cost a vector add).  The range check sees
+    // voffset + immediate: a lane without a node (voffset = QP_OOB) stays wholly out of range.
+    // The lane offset is made opaque first (not volatile: equal ones still merge): the optimiser otherwise pushes
+    // the constant through the select that forms it (node ? t * 8 : QP_OOB) and keeps one precomputed vector
+    // register per accessed column live across the whole kernel.
+    static constexpr int IMM = 0xFFF;
+    static __device__ __forceinline__ int vopq(int v) {
+        asm("" : "+v"(v));
+        return v;
+    }
+    __device__ __forceinline__ double ldk(int voff, int coff) const {
+        cnt(voff, coff, 8.0);
+        return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, vopq(voff) + (coff & IMM), coff & ~IMM, 0));
+    }
+    __device__ __forceinline__ qp_u4 ld4k(int voff, int coff) const {
+        cnt(voff, coff, 16.0);
+        return __builtin_amdgcn_raw_buffer_load_b128(rs, vopq(voff) + (coff & IMM), coff & ~IMM, 0);
+    }
+    __device__ __forceinline__ void stk(int voff, int coff, double v) const {
+        cnt(voff, coff, 8.0);
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(qp_u2, v), rs, vopq(voff) + (coff & IMM), coff & ~IMM, 0);
     }
 };
 // keep a value opaque to the optimiser (volatile: re-derived where it is used, never hoisted)
@@ -497,7 +541,11 @@ __device__ __forceinline__ void qp_phase_c(double* lds, const QPRepC* d, double 
     }
 }
 
-template <class C>
+// KC: the node count K at compile time (0: T.K at run time).  With KC set, every workspace offset (the column stride,
+// the packet and factor-block bases), the LDS offsets of the K-sized blocks and the chunk geometry are constants;
+// the workspace layout and the arithmetic are those of the KC = 0 instantiation of the same class (a warm start
+// written by one is valid for the other).  The host picks KC = T.K where it is compiled (qp_inst.hpp QPKSpec).
+template <class C, int KC = 0>
 __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NQ = C::NQ, NR = C::NR, NG = C::NG, NS = C::NS,
                   NO = C::NO, NC = C::NC, NB = C::NB, PKT = C::PKT, NV = C::NV, NVA = C::NVA;
@@ -506,7 +554,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     constexpr int CPF = NX > 8 ? 2 : QP_CPF;
     extern __shared__ double lds[];
     const scvx_qp_template& T = a.T;
-    const int K = T.K, lane = threadIdx.x, t = lane;
+    const int K = KC > 0 ? KC : T.K, lane = threadIdx.x, t = lane;
     // dispatch order: workgroups start in index order as slots free up, so when the agents outnumber the resident
     // waves (C4: 4096 agents, 1024 at a time) the host can deal the longest solves first (scvx_qp_solve_batched_ordered);
     // an entry outside [0, N) falls back to the workgroup's own index
@@ -572,8 +620,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     wb.rs = __builtin_amdgcn_make_buffer_rsrc(ws, (short)0, (int)(a.ws_agent * 8), 0x00020000);
     const int colb = K * 8;      // bytes per workspace column (one double per node)
     const int vt = act ? t * 8 : QP_OOB;  // this lane's element of a stage-minor column
-    const int PKB = C::NCOL * colb;       // byte offset of the packets [t][GPK]
-    const int FBB = PKB + K * C::GPK * 8;  // byte offset of the factor output blocks [t][FBS]
+    const int PKB = qp_even(C::NCOL * K) * 8;      // byte offset of the packets [t][GPK] (16-byte aligned)
+    const int FBB = PKB + qp_even(K * C::GPK) * 8;  // byte offset of the factor output blocks [t][FBS] (likewise)
     const int vpk = act ? t * C::GPK * 8 : QP_OOB;
     const int vfb = act ? t * C::FBS * 8 : QP_OOB;
     // Loads go through `vcur` / `vpcur`, this lane's offsets re-derived (opaquely) at the start of every
@@ -586,10 +634,31 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         vcur = qp_opaque(vt);
         vpcur = qp_opaque(vpk);
     };
-    auto cld = [&](int c) __attribute__((always_inline)) -> double { return wb.ld(vcur, c * colb); };
-    auto cst = [&](int c, double v) __attribute__((always_inline)) { wb.st(vt, c * colb, v); };
+    // workspace access at lane offset `v` plus a uniform offset `off` that is a compile-time constant where K is
+    // (QPBuf::ldk / stk: immediate field + shared 4 KB window); `add` is a further compile-time constant, which the
+    // runtime-K form adds to the lane offset (the immediate field) and the K-specialised form to `off`
+    auto wld = [&](int v, int off, int add = 0) __attribute__((always_inline)) -> double {
+        if constexpr (KC > 0) return wb.ldk(v, off + add);
+        else return wb.ld(v + add, off);
+    };
+    // two consecutive doubles from a 16-byte aligned address
+    auto wld2 = [&](double* dst, int v, int off, int add = 0) __attribute__((always_inline)) {
+        qp_u4 w;
+        if constexpr (KC > 0) w = wb.ld4k(v, off + add);
+        else w = wb.ld4(v + add, off);
+        qp_u2 lo, hi;
+        lo.x = w.x; lo.y = w.y; hi.x = w.z; hi.y = w.w;
+        dst[0] = __builtin_bit_cast(double, lo);
+        dst[1] = __builtin_bit_cast(double, hi);
+    };
+    auto wst = [&](int v, int off, double x) __attribute__((always_inline)) {
+        if constexpr (KC > 0) wb.stk(v, off, x);
+        else wb.st(v, off, x);
+    };
+    auto cld = [&](int c) __attribute__((always_inline)) -> double { return wld(vcur, c * colb); };
+    auto cst = [&](int c, double v) __attribute__((always_inline)) { wst(vt, c * colb, v); };
     // element g of this lane's (global) packet
-    auto pld = [&](int g) __attribute__((always_inline)) -> double { return wb.ld(vpcur, PKB + g * 8); };
+    auto pld = [&](int g) __attribute__((always_inline)) -> double { return wld(vpcur, PKB + g * 8); };
     // Batched loads: ldn issues the loads of n consecutive columns, hold pins values in registers.
     // Issue every load of a phase first and hold them before the first use, so the phase pays one
     // memory round trip (the scheduler otherwise serialises load -> wait -> use under pressure).
@@ -599,8 +668,16 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     };
     // n consecutive elements of this lane's factor output block, from block offset b0
     auto ldb = [&](double* dst, int b0, int n) __attribute__((always_inline)) {
+        // (a sub-block start is even, FBS is even and FBB 16-byte aligned: two elements per load; the callers'
+        // b0 are constants, so the test folds)
+        if ((b0 & 1) == 0) {
 #pragma unroll
-        for (int e = 0; e < n; ++e) dst[e] = wb.ld(vfb, FBB + (b0 + e) * 8);
+            for (int e = 0; e + 1 < n; e += 2) wld2(dst + e, vfb, FBB + (b0 + e) * 8);
+            if (n & 1) dst[n - 1] = wld(vfb, FBB + (b0 + n - 1) * 8);
+        } else {
+#pragma unroll
+            for (int e = 0; e < n; ++e) dst[e] = wld(vfb, FBB + (b0 + e) * 8);
+        }
     };
     // (n = 12 classes: not held -- their 144-element blocks would occupy the register file and spill;
     // the compiler then interleaves the loads with their uses instead)
@@ -610,7 +687,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             for (int e = 0; e < n; ++e) asm volatile("" : "+v"(v[e]));
         }
     };
-    auto pst = [&](int e, double v) __attribute__((always_inline)) { wb.st(vpk, PKB + e * 8, v); };
+    auto pst = [&](int e, double v) __attribute__((always_inline)) { wst(vpk, PKB + e * 8, v); };
 
     constexpr int V_M = C::L_M, V_PI0 = C::L_PI0, V_XE = C::L_XE, V_XI0 = C::L_XI0, V_R2F = C::L_R2F,
                   V_YI = C::L_YI, V_YF = C::L_YF, V_DYI = C::L_DYI, V_DYF = C::L_DYF, V_PIV = C::L_PIV,
@@ -743,7 +820,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int j = 0; j < NU; ++j) cst(C::C_UB + j, act ? a.Uref[(agent * K + t) * NU + j] : 0.0);
         if (warm) {   // the last solve's primal / dual state stays in place; its y_init / y_fin to LDS
-            if (lane < 2 * NX) lds[V_YI + lane] = wb.ld(vt, C::C_WY * colb);   // (V_YF = V_YI + NX)
+            if (lane < 2 * NX) lds[V_YI + lane] = wld(vt, C::C_WY * colb);   // (V_YF = V_YI + NX)
         } else {
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
@@ -764,7 +841,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     // C_{t-1} (column-major as disc) of this node, from the transposed disc of node t-1 (the lane below)
     auto load_cp = [&](double* Cp) __attribute__((always_inline)) {
 #pragma unroll
-        for (int e = 0; e < NX * NU; ++e) Cp[e] = wb.ld(vcur - 8, (C::C_DT + NX * NX + NX * NU + e) * colb);
+        for (int e = 0; e < NX * NU; ++e) Cp[e] = wld(vcur - 8, (C::C_DT + NX * NX + NX * NU + e) * colb);
         hold(Cp, NX * NU);
 #pragma unroll
         for (int e = 0; e < NX * NU; ++e) Cp[e] = (t > 0) ? Cp[e] : 0.0;
@@ -1518,7 +1595,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 const int tj = cs0 + j;
                 const int vo = (cact && j < CL && tj < cs1) ? (C::B_CH + ce * NX) * 8 + tj * C::FBS * 8 : QP_OOB;
 #pragma unroll
-                for (int k = 0; k < NX; ++k) ar[j][k] = wb.ld(vo + k * 8, FBB);
+                for (int k = 0; k < NX; ++k) {
+                    if constexpr (NX % 2 == 0) { if (!(k & 1)) wld2(&ar[j][k], vo, FBB, k * 8); }   // rows start even
+                    else ar[j][k] = wld(vo, FBB, k * 8);
+                }
             }
 #pragma unroll
             for (int c = 0; c < NX; ++c) ph[c] = (c == ce) ? 1.0 : 0.0;
@@ -1626,7 +1706,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 const bool ok = cact && j < CL && tj >= cs0;
                 const int vo = ok ? (C::B_CH + ce) * 8 + tj * C::FBS * 8 : QP_OOB;
 #pragma unroll
-                for (int k = 0; k < NX; ++k) ac[j][k] = wb.ld(vo + k * NX * 8, FBB);
+                for (int k = 0; k < NX; ++k) ac[j][k] = wld(vo, FBB, k * NX * 8);
                 gc[j] = lds[V_G + (ok ? tj : 0) * NX + (ce < NX ? ce : 0)];
             }
             auto chainT = [&](double q, const double* a, double g) __attribute__((always_inline)) -> double {
@@ -1932,7 +2012,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 const bool ok = cact && j < CL && tj < cs1;
                 const int vo = ok ? (C::B_CH + ce * NX) * 8 + tj * C::FBS * 8 : QP_OOB;
 #pragma unroll
-                for (int k = 0; k < NX; ++k) ar[j][k] = wb.ld(vo + k * 8, FBB);
+                for (int k = 0; k < NX; ++k) {
+                    if constexpr (NX % 2 == 0) { if (!(k & 1)) wld2(&ar[j][k], vo, FBB, k * 8); }   // rows start even
+                    else ar[j][k] = wld(vo, FBB, k * 8);
+                }
                 fr[j] = lds[V_G + (ok ? tj : 0) * NX + (ce < NX ? ce : 0)];
             }
             auto chainF = [&](double x, const double* a, double f) __attribute__((always_inline)) -> double {
@@ -2118,7 +2201,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     constexpr int NSR = SGS ? 1 : NSA;
     double z[NZ], y[NX], sq[NQ], lq[NQ], av[NGA], ub[NU], sg[NSR][3], sb[NSR];
     auto sgv = [&](int q, int i) __attribute__((always_inline)) -> double {
-        if constexpr (SGS) return wb.ld(qp_opaque(vt), (C::C_SOFT + q * 4 + i) * colb);
+        if constexpr (SGS) return wld(qp_opaque(vt), (C::C_SOFT + q * 4 + i) * colb);
         else return i < 3 ? sg[q][i] : sb[q];
     };
     // virtual control state of this node (VC classes, lanes t < K-1): nu, e, and per component the slacks /
@@ -2617,7 +2700,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int e = 0; e < NU * NU; ++e) Wu[e] = (e / NU == e % NU) ? 1.0 : 0.0;
         dyn_residual(z, [&](int e) __attribute__((always_inline)) -> double {
-            if constexpr (DSTRM) return wb.ld(qp_opaque(vt), (C::C_DT + e) * colb);
+            if constexpr (DSTRM) return wld(qp_opaque(vt), (C::C_DT + e) * colb);
             else return dt[e];
         }, rp);
         assemble(true, Wu, rp);
@@ -2825,7 +2908,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     double col[NX];
                     const int vo = qp_opaque(vt);
 #pragma unroll
-                    for (int i = 0; i < NX; ++i) col[i] = wb.ld(vo, (C::C_DT + k * NX + i) * colb);
+                    for (int i = 0; i < NX; ++i) col[i] = wld(vo, (C::C_DT + k * NX + i) * colb);
 #pragma unroll
                     for (int i = 0; i < NX; ++i) rp[i] -= col[i] * z[k];
 #pragma unroll
@@ -3421,11 +3504,12 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 
 #ifndef __HIPCC_RTC__
 // launch helpers (qp_capi.hip picks the instantiation)
-template <class C>
+template <class C, int KC = 0>
 int qp_launch(const QPArgs& a, hipStream_t st) {
+    if (KC > 0 && a.T.K != KC) return set_error(SCVX_EINVAL, "qp: K-specialised instantiation launched at another K");
     const size_t lds = sizeof(double) * (size_t)C::lds_doubles(a.T.K);
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)qp_ipm_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(qp_ipm_kernel<C>, dim3(a.N), dim3(WAVE), lds, st, a);
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)qp_ipm_kernel<C, KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((qp_ipm_kernel<C, KC>), dim3(a.N), dim3(WAVE), lds, st, a);
     return check_launch("qp_ipm_kernel");
 }
 #endif
