@@ -33,13 +33,13 @@ namespace {
 // csrc/foh_body.hpp, csrc/intersample_body.hpp and include/scvx_hip.h as string literals (build/*.inc, generated
 // by the Makefile)
 const char* const kFohBody =
-#include "foh_body.inc"
+#include "foh_body.hpp.inc"
     ;
 const char* const kIsBody =
-#include "intersample_body.inc"
+#include "intersample_body.hpp.inc"
     ;
 const char* const kScvxHdrF =
-#include "scvx_hip_h.inc"
+#include "scvx_hip.h.inc"
     ;
 
 bool is_zero(const char* e) {

@@ -7,9 +7,10 @@
 
 #include "common.hpp"
 #include "qp_caps.hpp"
-#include "qp_ipm.hpp"
+#include "qp_layout.hpp"
 #include "scvx_hip.h"
 #include "subproblem_rtc.hpp"
+#include "wave_ops.hpp"
 
 namespace scvx {
 int qp_launch_di(int idx, const QPArgs& a, hipStream_t st);
@@ -78,9 +79,8 @@ int qp_check(const scvx_qp_template* T, int N, QPClass& c) {
     c = QPClass{};
     c.nx = T->n_x; c.nu = T->n_u;
     if (T->model_id == SCVX_MODEL_RUNTIME) {
-        // the kernel's limits (subproblem_rtc.hpp, shared with scvx_rtc_subproblem_compile)
-        if (const char* bad = rtc_qp_class_error(T->n_x, T->n_u, T->n_box, T->n_obs, T->j_max, T->w_nu > 0.0 ? 1 : 0,
-                                                 T->K))
+        // the kernel's limits (qp_layout.hpp, shared with scvx_rtc_subproblem_compile)
+        if (const char* bad = qp_class_error(T->n_x, T->n_u, T->n_box, T->n_obs, T->j_max, T->w_nu > 0.0 ? 1 : 0, T->K))
             return set_error(SCVX_EUNSUPPORTED, bad);
         c.rt = true;
         c.nb = T->n_box; c.no = T->n_obs; c.nc = T->j_max; c.vc = T->w_nu > 0.0 ? 1 : 0;
@@ -99,8 +99,7 @@ int qp_check(const scvx_qp_template* T, int N, QPClass& c) {
 }
 
 size_t ws_bytes(const QPClass& c, int N, int K) {
-    const int nv = c.vc ? c.nx : 0, ns = c.no + c.nc, ng = c.no + (c.nc > 0 ? 1 : 0);
-    return sizeof(double) * (size_t)N * (size_t)qp_ws_doubles(c.nx, c.nu, c.nb, ns, ng, K, nv, c.nc);
+    return sizeof(double) * (size_t)N * (size_t)qp_layout(c.nx, c.nu, c.nb, c.no, c.nc, c.vc).ws_doubles(K);
 }
 }  // namespace
 

@@ -44,502 +44,18 @@
 #endif
 #include <type_traits>
 
-#include "scvx_hip.h"
-#include "wave_ops.hpp"
+#include "qp_consts.hpp"
+#include "qp_factor_phase.hpp"
 
 namespace scvx {
 
-struct QPArgs {
-    scvx_qp_template T;
-    int N;
-    const double* disc;
-    const double* sigma;
-    const double* Xref;
-    const double* Uref;
-    const double* x_init;
-    const double* x_final;
-    const double* tr;
-    const double* coll_rows;
-    const int32_t* coll_count;
-    const int32_t* warm; // per agent: start from the state this workspace holds from the agent's last solve
-    double* X;
-    double* U;
-    double* slack_coll;
-    double* nu;          // virtual control [N][K-1][n] (w_nu > 0 classes)
-    double* obj;
-    int32_t* status;
-    int32_t* iters;
-    double* ws;          // workspace
-    long long ws_agent;  // doubles per agent
-    double* trace;       // optional per-iteration diagnostics of agent `trace_agent` (or nullptr)
-    int trace_agent, trace_cap;
-    const int32_t* order;  // optional dispatch order: workgroup b solves agent order[b] (nullptr: agent b)
-};
-
-// ---- sizes shared by host (workspace / LDS bytes) and device
-constexpr int qp_dstr(int nx, int nu) { return nx * (nx + 2 * nu + 2); }
-// stiff trust-region facets (the coupled classes, n <= 8, 2 <= m <= 4; see QPCfg::STF): the 2^m facet weights, their
-// folded sum (diagonal and upper off-diagonals of sum_f D_f g_f g_f') and their maximum ride in the packet; at most
-// m-1 of them stay explicit per stage
-constexpr bool qp_stf(int nx, int nu, int nc) { return nx <= 8 && nu >= 2 && nu <= 4 && nc > 0; }
-constexpr int qp_pm(int nx, int nu, int nc) { return qp_stf(nx, nu, nc) ? nu - 1 : 0; }
-constexpr int qp_nfd(int nx, int nu, int nc) { return qp_stf(nx, nu, nc) ? (1 << nu) + 2 + nu * (nu - 1) / 2 : 0; }
-constexpr int qp_pkt(int nx, int nu, int nv = 0, int nc = 0) {
-    return 2 * nx * nx + 4 * nx * nu + nu * nu + nx + nv + qp_nfd(nx, nu, nc);
-}
-// global packet: n <= 8 compact (Q as its diagonal + the 3 off-diagonals of the position block, S, R upper
-// packed, e, A, Bt (column-major), C_{t-1}, the virtual control's D) -- expanded to the LDS packet layout by the
-// factor's prefetch through a per-lane gather table; n = 12 dense (the LDS layout itself, QPCfg::DPK)
-constexpr int qp_gpk(int nx, int nu, int nv = 0, int nc = 0) {
-    return nx > 8 ? qp_pkt(nx, nu, nv, nc)
-                  : (nx + 3) + nx * nu + nu * (nu + 1) / 2 + nx + nx * nx + 2 * nx * nu + nv + qp_nfd(nx, nu, nc);
-}
-constexpr int qp_even(int x) { return (x + 1) & ~1; }
-// workspace columns (K doubles each: one per node) of a capacity class
-constexpr int qp_ncol(int nx, int nu, int nb, int ns, int ng, int nv = 0) {
-    // disc^T | Bt | soft rows | groups | rd | r1a | cP | ub | node state | SOC | virtual control state |
-    // warm-start state (row duals, initial / terminal multipliers)
-    return qp_dstr(nx, nu) + nx * nu + 4 * ns + 4 * ng + (nx + nu) + ng + ((1 << nu) + 2 * nb + ns + ng) + nu +
-           ((nx + nu) + nx + 2 * (nu + 1) + ng) + (3 * (nu + 1) + 1 + (nu + 1)) + 11 * nv +
-           ((1 << nu) + 2 * nb + ns + ng) + 1 + (nx > 8 ? 2 * ((1 << nu) + 2 * nb + ns + ng) : 0);
-}
-// factor outputs per stage (stage-major block): K, kappa, LD, W2, P, Pi, u, Acl, [virtual control: G^-1 P,
-// G^-1 Pi, G^-1, Acl~], [stiff facets: Gamma, Gamma_kappa, W, C^-1, facet indices], one junk slot (the global
-// store of lanes without an output of their own).  Every sub-block starts on an even element (one padding double
-// after a sub-block of odd size; the small block W | C^-1 | indices stays contiguous) and the block size is even:
-// with the 16-byte region bases of qp_ws_doubles the lane-parallel passes read a sub-block two doubles per load
-// (QPCfg::B_* is the same chain of qp_even; C3: 178 -> 180 doubles)
-constexpr int qp_fbs(int nx, int nu, int nv = 0, int nc = 0) {
-    const int pm = qp_pm(nx, nu, nc);
-    int o = 0;
-    o = qp_even(o + nu * nx);   // K
-    o = qp_even(o + nu * nx);   // kappa
-    o = qp_even(o + nu * nu);   // LD
-    o = qp_even(o + nu * nx);   // W2
-    o = qp_even(o + nx * nx);   // P
-    o = qp_even(o + nx * nx);   // Pi
-    o = qp_even(o + nx);        // u
-    o = qp_even(o + nx * nx);   // Acl
-    for (int i = 0; i < 4; ++i) o = qp_even(o + nv * nx);   // G^-1 P, G^-1 Pi, G^-1, Acl~
-    o = qp_even(o + pm * nx);   // Gamma
-    o = qp_even(o + pm * nx);   // Gamma_kappa
-    o = o + nu * pm + pm * pm + pm;   // W | C^-1 | indices: one contiguous small block
-    return qp_even(o + 1);      // junk slot
-}
-// per agent: columns [c][K], packets [K][GPK], factor blocks [K][FBS], each region from a 16-byte boundary (the
-// column and the packet region rounded up to an even number of doubles: odd K) -- only the K nodes: lanes >= K
-// address past the end of the buffer (loads read 0, stores are dropped), so the agent's footprint is
-// what its nodes touch (C3: 1024 agents x 233 KB stay inside the 256 MB Infinity Cache)
-// n = 12 classes: the factor's per-lane phase descriptors, [repetition][lane] x 16 bytes (QPRepC + pad), after the
-// factor blocks (agent-independent, rewritten at each sweep; see the factor sweep)
-constexpr int qp_nrep(int nx, int nu) {
-    return (2 * nx * nx + 2 * nx * nu + 2 * nx + 63) / 64 + (nx * nx + nu * nx + nu * nu + 63) / 64 + (4 * nx * nx + 63) / 64;
-}
-constexpr int qp_dtab(int nx, int nu) { return nx > 8 ? qp_nrep(nx, nu) * 64 * 2 : 0; }
-constexpr long long qp_ws_doubles(int nx, int nu, int nb, int ns, int ng, int K, int nv = 0, int nc = 0) {
-    return (long long)qp_even(K * qp_ncol(nx, nu, nb, ns, ng, nv)) + qp_even(K * qp_gpk(nx, nu, nv, nc)) +
-           (long long)K * qp_fbs(nx, nu, nv, nc) + qp_dtab(nx, nu);
-}
-// LDS doubles of a class (QPCfg::lds_doubles, written out for the host of a runtime-compiled class, which
-// has no QPCfg instantiation; QPCfg asserts that both agree)
-constexpr int qp_lds_doubles(int nx, int nu, int nb, int no, int nc, int vc, int K) {
-    const int nv = vc ? nx : 0;
-    const int pkt = qp_pkt(nx, nu, nv, nc);
-    const int f_sink = pkt + 5 * nx * nx + 5 * nx * nu + nu * nu;
-    const int f_end = qp_even(f_sink + (nx > 8 ? nx : 8) + 4 * nv * nx);
-    const int nr = (1 << nu) + 2 * nb + no + nc + no + (nc > 0 ? 1 : 0);
-    const int l_var = qp_even(f_end + 2 * nx * nx + 8 * nx + 1 + 4) + 16 + (nx > 8 ? 0 : 2 * nr * 64);
-    return l_var + K * nx + (K + 1) * nx + (nx <= 8 ? 8 * nx * nx : 0);
-}
-// byte offset of every access of a lane without a node (t >= K): beyond num_records of any workspace
-constexpr int QP_OOB = 0x40000000;
-// warm start: floor of every slack and dual of the previous iterate (scaled units; oracle/scvx_cpu.cpp)
-constexpr double QP_WARM_ETA = 1e-3;
-// ... except that a row's dual floor is min(QP_WARM_ETA, QP_WARM_KAPPA / s) at its recomputed slack s: a row far from
-// active (box rows, obstacle rows away from the trajectory: s ~ 1..10) keeps a dual near its last, tiny value instead
-// of 1e-3, so the start's complementarity s lambda is ~1e-5 there, not ~1e-2.  The warm solve starts ~100x closer
-// to the end game: on the CPU twin over the bench's 25 steps, the slowest agent's IPM iterations summed over the
-// timed steps fall 171 -> 132 (per-agent rule) and 240 -> 201 (global rule), seeds 2 and 3 alike
-constexpr double QP_WARM_KAPPA = 1e-5;
-// stiff trust-region facet: its barrier weight D = lambda / s above QP_STIFF x the largest diagonal entry of the rest
-// of the stage's input Hessian Rhat (oracle/scvx_cpu.cpp STIFF_RATIO, the same rule)
-constexpr double QP_STIFF = 1e6;
-
-// a / b for the per-row barrier quantities (l / s, the rows' Newton terms): the hardware reciprocal, two Newton
-// steps and a product (~1.5 ulp, six instructions) instead of the correctly rounded division sequence (eleven,
-// with a longer dependent chain); these run once per row per phase on every node
-__device__ __forceinline__ double qp_div(double a, double b) {
-#ifdef QP_EXACT_DIV   // diagnostics build (tools/qp_div_accuracy.py): the correctly rounded division of round 4
-    return a / b;
-#endif
-    double r = __builtin_amdgcn_rcp(b);
-    r = fma(fma(-b, r, 1.0), r, r);
-    r = fma(fma(-b, r, 1.0), r, r);
-    return a * r;
-}
-// fraction-to-boundary of the end game (affine step >= 0.99).  In the warm-started Jacobi loop almost every
-// solve is an end game from its first iteration: each step is a full Newton step up to this fraction, so
-// the gap falls by 1 / (1 - QP_TAU_END) per iteration.  0.999 took the C3 bulk 5 iterations, 1 - 1e-5 takes
-// it 3 (oracle/scvx_cpu.cpp, the same rule; 1 - 1e-6 lengthened the tail: measured on the twin over the
-// bench's 25 steps)
-constexpr double QP_TAU_END = 0.99999;
-// chunked solve chains (NX <= 8): the K-1 transitions are cut into QP_NCH chunks, one per 8-lane group; a
-// chunk holds at most QP_CLM transitions (K <= 64)
-constexpr int QP_NCH = 8, QP_CLM = 8;
-
-// VC_ = 1: the virtual-control class (scvx_qp_template.w_nu > 0): nu_t in every dynamics row, priced
-// w_nu ||nu_t||_1 through its epigraph -e <= nu <= e.  nu is eliminated inside each Riccati stage
-// (G = D + P_{t+1}, D = the node's nu curvature after e is eliminated), e and the 2 n rows per node
-// live in workspace columns, not in the LDS row state.
+// A capacity class of the kernel: its layout (csrc/qp_layout.hpp: the one statement of every offset and size) as a
+// compile-time constant.  VC_ = 1: the virtual-control class (scvx_qp_template.w_nu > 0).
 template <int NX_, int NU_, int NB_, int NO_, int NC_, int VC_ = 0>
 struct QPCfg {
-    static constexpr int NX = NX_, NU = NU_, NB = NB_, NO = NO_, NC = NC_, VC = VC_;
-    static constexpr int NV = VC_ ? NX_ : 0, NVA = NV > 0 ? NV : 1;
-    static constexpr int NZ = NX + NU, NQ = NU + 1, NTR = 1 << NU;
-    static constexpr int NS = NO + NC;                // soft halfspace rows
-    static constexpr int NG = NO + (NC > 0 ? 1 : 0);  // slack groups (one per obstacle, one shared)
-    static constexpr int R_BOX = NTR, R_OBS = NTR + 2 * NB, R_COL = R_OBS + NO, R_GRP = R_COL + NC;
-    static constexpr int NR = R_GRP + NG;
-    static constexpr int DSTR = qp_dstr(NX, NU);
-    // factor packet [t][PKT]: node Hessian Q|S|R, e, then the constant A (column-major) | Bt
-    // column-major | Bt row-major | C_{t-1} (column-major).  Every dot product of the factor
-    // phases then reads two contiguous LDS vectors.
-    // stiff trust-region facets (STF: the coupled classes, n <= 8 and 2 <= m <= 4): the node's R leaves the 2^m
-    // facets' D g g' out; their weights D_f, their folded sum and max ride in the packet (P_FD) and factor phase 3
-    // folds them back into Rhat, all but at most PM = m-1 stiff ones, which stay explicit stage unknowns (Woodbury;
-    // see the factor).  The uncoupled classes (C3) fold the facets into R as before: no stiff facet has failed a
-    // C3 solve, and the stage work costs ~13 % of an IPM iteration there (round 5 A/B).
-    static constexpr bool STF = qp_stf(NX_, NU_, NC_);
-    static constexpr int NFD = qp_nfd(NX_, NU_, NC_), PM = qp_pm(NX_, NU_, NC_), PMA = PM > 0 ? PM : 1;
-    // packet: the facet weights | their folded sum (diagonal, upper off-diagonals) | their maximum
-    static constexpr int NFO = NU_ * (NU_ - 1) / 2;
-    static constexpr int P_Q = 0, P_S = P_Q + NX * NX, P_R = P_S + NX * NU, P_E = P_R + NU * NU,
-                         P_A = P_E + NX, P_BT = P_A + NX * NX, P_BTR = P_BT + NX * NU, P_C = P_BTR + NX * NU,
-                         P_D = P_C + NX * NU, P_FD = P_D + NV, PKT = P_FD + NFD;
-    static_assert(PKT == qp_pkt(NX, NU, NV, NC), "packet size");
-    // global packet (compact, n <= 8; qp_gpk): Q diagonal | Q position-block off-diagonals (0,1) (0,2) (1,2) |
-    // S | R upper packed | e | A (column-major) | Bt (column-major) | C_{t-1} (column-major) | D
-    static constexpr int G_QD = 0, G_QO = G_QD + NX, G_S = G_QO + 3, G_R = G_S + NX * NU,
-                         G_E = G_R + NU * (NU + 1) / 2, G_A = G_E + NX, G_BT = G_A + NX * NX, G_C = G_BT + NX * NU,
-                         G_D = G_C + NX * NU, G_FD = G_D + NV;
-    // n = 12 (DPK): the global packet has the LDS layout element for element.  The compact form needs a per-lane
-    // gather table of PFN offsets live across the factor sweep; at n = 12 the register allocator spilled it to
-    // scratch, and every reload waited for the packet prefetches in flight.  The dense prefetch is one
-    // contiguous load per 64 elements; Q's structural zeros are written once per solve (setup), with the
-    // constant A | Bt | Bt row-major | C_{t-1}; the node phase writes Q's nonzeros (both triangles), S, R (both
-    // halves), e, D.  (n <= 8 keeps the compact form: its 3-entry table costs nothing, the dense packet's extra
-    // traffic does: C3 780 -> 742 SCvx-it/s, A/B round 4.)
-    static constexpr bool DPK = NX > 8;
-    static constexpr int GPK = DPK ? PKT : G_FD + NFD;
-    static_assert(GPK == qp_gpk(NX, NU, NV, NC), "global packet size");
-    static_assert(NX >= 3, "the position block is 3 x 3");
-    // global packet element of LDS packet element e (-1: a structural zero)
-    static constexpr int gsrc(int e) {
-        if (DPK) return e;
-        if (e < P_S) {
-            const int i = e / NX, j = e % NX;
-            if (i == j) return G_QD + i;
-            if (i < 3 && j < 3) return G_QO + i + j - 1;  // (0,1) -> 0, (0,2) -> 1, (1,2) -> 2
-            return -1;
-        }
-        if (e < P_R) return G_S + (e - P_S);
-        if (e < P_E) {
-            const int i = (e - P_R) / NU, j = (e - P_R) % NU, p = i < j ? i : j, q = i < j ? j : i;
-            return G_R + p * NU - p * (p - 1) / 2 + (q - p);
-        }
-        if (e < P_A) return G_E + (e - P_E);
-        if (e < P_BT) return G_A + (e - P_A);
-        if (e < P_BTR) return G_BT + (e - P_BT);
-        if (e < P_C) {
-            const int i = (e - P_BTR) / NU, j = (e - P_BTR) % NU;
-            return G_BT + j * NX + i;
-        }
-        if (e < P_D) return G_C + (e - P_C);
-        if (e < P_FD) return G_D + (e - P_D);
-        return G_FD + (e - P_FD);
-    }
-    // global packet index of the node-phase outputs e, D and of the constant blocks
-    static constexpr int gE = DPK ? P_E : G_E, gD = DPK ? P_D : G_D, gS = DPK ? P_S : G_S, gA = DPK ? P_A : G_A,
-                         gBT = DPK ? P_BT : G_BT, gC = DPK ? P_C : G_C, gFD = DPK ? P_FD : G_FD;
-    static_assert(NX <= 16, "the solve chains broadcast within one 16-lane row");
-    // factor outputs: stage-major blocks [t][FBS] (coalesced stores from the element-parallel
-    // factor; each lane-parallel pass reads its own stage's block)
-    static constexpr int B_K = 0;                  // K      NU x NX
-    // (every sub-block on an even element, padded where the one before has an odd size: 16-byte loads, ldb)
-    static constexpr int B_KAP = qp_even(B_K + NU * NX);    // kappa  NU x NX
-    static constexpr int B_LD = qp_even(B_KAP + NU * NX);   // LDL' of Rhat: L[i][j] (i > j), 1/d_i on the diagonal
-    static constexpr int B_W2 = qp_even(B_LD + NU * NU);    // W2 = Bt' Pi_{t+1}  NU x NX
-    static constexpr int B_P = qp_even(B_W2 + NU * NX);     // P_t
-    static constexpr int B_PI = qp_even(B_P + NX * NX);     // Pi_t
-    static constexpr int B_U = qp_even(B_PI + NX * NX);     // P_{t+1} e_t
-    static constexpr int B_ACL = qp_even(B_U + NX);         // Acl_t = A_t + Bt_t K_t (row-major)
-    // virtual control (VC): G^-1 P_{t+1}, G^-1 Pi_{t+1}, G^-1 (column-major), the chain matrix
-    // Acl~ = G^-1 D Acl (row-major)
-    static constexpr int B_YP = qp_even(B_ACL + NX * NX), B_YPI = qp_even(B_YP + NV * NX),
-                         B_GI = qp_even(B_YPI + NV * NX), B_ACL2 = qp_even(B_GI + NV * NX);
-    static constexpr int B_CH = NV > 0 ? B_ACL2 : B_ACL;  // what the solve chains read
-    // stiff facets (STF): Gamma = -C^-1 G' R0^-1 Sh and Gamma_kappa = -C^-1 G' R0^-1 W2 (PM x NX, row-major: the
-    // multiplier steps nu = Gamma xi + Gamma_kappa mu + gamma0), then W = R0^-1 G (NU x PM), C^-1 (PM x PM) and the
-    // stiff facets' indices (PM, -1 = empty slot)
-    static constexpr int B_GAM = qp_even(B_ACL2 + NV * NX), B_GAK = qp_even(B_GAM + PM * NX),
-                         B_WS = qp_even(B_GAK + PM * NX), B_CI = B_WS + NU * PM, B_SF = B_CI + PM * PM;
-    static constexpr int NSMB = NU * PM + PM * PM + PM;   // W | C^-1 | indices: one small block
-    static constexpr int B_JNK = B_SF + PM;  // junk slot (stores of lanes without an output)
-    static constexpr int FBS = qp_even(B_JNK + 1);
-    static_assert(FBS == qp_fbs(NX, NU, NV, NC), "factor block");
-    // stage-minor workspace columns
-    static constexpr int C_DT = 0;                 // disc, transposed: A (col-major) | B | C | S | z
-    static constexpr int C_BT = C_DT + DSTR;       // Bt_t (row-major)
-    static constexpr int C_SOFT = C_BT + NX * NU;  // soft rows (g0, g1, g2, b)
-    static constexpr int C_GRP = C_SOFT + 4 * NS;  // per group: Hpa/Haa (3), 1/Haa
-    static constexpr int C_RD = C_GRP + 4 * NG;    // dual residual (x, u part)
-    static constexpr int C_R1A = C_RD + NZ;        // group part of the current Newton rhs
-    static constexpr int C_CP = C_R1A + NG;        // predictor products ds_a dl_a per row
-    static constexpr int C_UB = C_CP + NR;         // reference input ubar_t
-    // node state
-    static constexpr int C_Z = C_UB + NU, C_Y = C_Z + NZ, C_SQ = C_Y + NX,
-                         C_LQ = C_SQ + NQ, C_AV = C_LQ + NQ;
-    // SOC scaling of the current iteration: w (NQ), eta, W lam (NQ), rc (NQ), rho (NQ)
-    static constexpr int C_WV = C_AV + NG, C_ETA = C_WV + NQ, C_LTQ = C_ETA + 1, C_RCQ = C_LTQ + NQ,
-                         C_RHO = C_RCQ + NQ;
-    // virtual control state (lanes t < K-1): nu, e, slacks s1 s2 and duals l1 l2 of the rows nu - e <= 0,
-    // -nu - e <= 0, the e part of the Newton rhs, the predictor products of the two rows, the dual residual
-    // (nu, e parts)
-    static constexpr int C_VN = C_RHO + NQ, C_VE = C_VN + NV, C_VS = C_VE + NV, C_VL = C_VS + 2 * NV,
-                         C_VRE = C_VL + 2 * NV, C_VCP = C_VRE + NV, C_VRD = C_VCP + 2 * NV;
-    // warm start: the row duals lambda_r at the last iterate (NR), and y_init (lanes 0..NX-1) / y_fin (lanes
-    // NX..2NX-1) in one column (needs K >= 2 NX: the host checks)
-    static constexpr int C_WL = C_VRD + 2 * NV, C_WY = C_WL + NR;
-    // row slacks / duals: LDS [r][lane] for n <= 8; for the n = 12 classes workspace columns (their 49 rows
-    // took 50 KB of LDS per agent, two waves per CU; in columns the class runs four)
-    static constexpr bool ROWG = NX > 8;
-    static constexpr int C_RS = C_WY + 1, C_RL = C_RS + (ROWG ? NR : 0);
-    static constexpr int NCOL = C_RL + (ROWG ? NR : 0);
-    static_assert(NCOL == qp_ncol(NX, NU, NB, NS, NG, NV), "column count");
-    // LDS (doubles, compile-time offsets except the K-sized blocks at the end):
-    // factor: the current stage's packet, P', Pi' (col-major), T1, T2 (col-major), W1, W2 (col-major), Qh,
-    // Sh (col-major), Rh, [K | kappa] (col-major), sink
-    static constexpr int F_RING = 0, F_PP = PKT, F_PIP = F_PP + NX * NX, F_T1 = F_PIP + NX * NX,
-                         F_T2 = F_T1 + NX * NX, F_W1 = F_T2 + NX * NU, F_W2 = F_W1 + NX * NX,
-                         F_QH = F_W2 + NU * NX, F_SH = F_QH + NX * NX, F_RH = F_SH + NU * NX,
-                         F_KK = F_RH + NU * NU, F_SINK = F_KK + 2 * NU * NX,
-                         // virtual control: G^-1 P, G^-1 Pi (column-major), Z = G^-1 D (row-major), Acl (column-major)
-                         F_YP = F_SINK + (NX > 8 ? NX : 8), F_YPI = F_YP + NV * NX, F_Z = F_YPI + NV * NX,
-                         F_ACLC = F_Z + NV * NX, F_END = qp_even(F_ACLC + NV * NX);
-    static constexpr int L_M = F_END, L_PI0 = L_M + NX * NX, L_XE = L_PI0 + NX * NX, L_XI0 = L_XE + NX,
-                         L_R2F = L_XI0 + NX, L_YI = L_R2F + NX, L_YF = L_YI + NX, L_DYI = L_YF + NX,
-                         L_DYF = L_DYI + NX, L_PIV = L_DYF + NX, L_ONE = L_PIV + NX, L_FLAG = L_ONE + 1,
-                         L_ST = qp_even(L_FLAG + 4), L_S = L_ST + 16, L_L = L_S + (NX > 8 ? 0 : NR * 64),
-                         L_VAR = L_L + (NX > 8 ? 0 : NR * 64);
-    // row slacks s / duals lambda [r][lane]; then K-sized: chain offsets g/f [K][NX], chain vectors [K+1][NX];
-    // then (chunked solve chains, NX <= 8) the chunk transition matrices Phi_c [QP_NCH][NX][NX]
-    static constexpr bool CHK = NX <= 8;
-    static constexpr int lds_doubles(int K) { return L_VAR + K * NX + (K + 1) * NX + (CHK ? QP_NCH * NX * NX : 0); }
-    static_assert(lds_doubles(50) == qp_lds_doubles(NX, NU, NB, NO, NC, VC, 50), "host LDS formula");
-    static_assert(4 * NV <= WAVE, "virtual control: one Gauss-Jordan column per lane");
+    static constexpr QPLay L = qp_layout(NX_, NU_, NB_, NO_, NC_, VC_);
+    static_assert(qp_class_error(NX_, NU_, NB_, NO_, NC_, VC_, 2, QP_LDS_DEVICE) == nullptr, "class outside the kernel's limits");
 };
-
-// packed phase descriptors (all operands are contiguous LDS vectors; the stage packet always sits at
-// F_RING, so every offset is stage-invariant):
-//   operand = LDS offset (15 bits)
-//   output  = LDS offset | accumulate << 15 | (global column + 1) << 17
-//   base    = LDS offset | kind << 16   (kind 0: none, 1: always, 2: last stage)
-__host__ __device__ constexpr int qp_dpk(int off, int) { return off; }
-
-// Agent workspace accessor: raw buffer loads/stores with the lane part of the address in one
-// VGPR (voffset) and the column part as a (rematerialisable) SGPR constant (soffset), so no
-// per-column 64-bit address is ever materialised in vector registers.
-typedef unsigned int qp_u2 __attribute__((ext_vector_type(2)));
-typedef unsigned int qp_u4 __attribute__((ext_vector_type(4)));
-// Every memory op of the factor sweep is unconditional: lanes with nothing to store write to the
-// junk slot of the stage block, and prefetch loads of padding / structurally zero packet elements
-// read past the end of the workspace (0).  A load or store under a divergent branch makes the
-// compiler's vmcnt accounting fall back to vmcnt(0), which drains the packet prefetches issued
-// stages ahead (measured: most of the factor's per-stage time).
-// solve-chain prefetch depth (stages of Acl / offsets held in registers ahead of the chain)
-constexpr int QP_CPF = 4;
-struct QPBuf {
-    __amdgpu_buffer_rsrc_t rs;
-#ifdef QP_BYTE_TRACE
-    // diagnostics build (tools/qp_bytes_trace.py): workspace bytes this lane requested since the last region stamp
-    // (lanes without a node address QP_OOB and move nothing); the stamps fold them into the trace buffer per region
-    mutable double nby = 0.0;
-    __device__ __forceinline__ void cnt(int voff, int soff, double b) const {
-        nby += (voff < QP_OOB && soff < QP_OOB) ? b : 0.0;
-    }
-#else
-    __device__ __forceinline__ void cnt(int, int, double) const {}
-#endif
-    __device__ __forceinline__ double ld(int voff, int soff) const {
-        soff = __builtin_amdgcn_readfirstlane(soff);  // uniform by construction
-        cnt(voff, soff, 8.0);
-        return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0));
-    }
-    __device__ __forceinline__ void st(int voff, int soff, double v) const {
-        soff = __builtin_amdgcn_readfirstlane(soff);
-        cnt(voff, soff, 8.0);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(qp_u2, v), rs, voff, soff, 0);
-    }
-    __device__ __forceinline__ qp_u4 ld4(int voff, int soff) const {
-        soff = __builtin_amdgcn_readfirstlane(soff);
-        cnt(voff, soff, 16.0);
-        return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
-    }
-    __device__ __forceinline__ void st4(int voff, int soff, qp_u4 v) const {
-        soff = __builtin_amdgcn_readfirstlane(soff);
-        cnt(voff, soff, 16.0);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, soff, 0);
-    }
-    // A byte offset known at compile time (the K-specialised instantiations: qp_ipm_kernel's KC) is split: its low
-    // 12 bits join voffset, where the backend folds a constant addend into the instruction's immediate field, and
-    // the 4 KB window above them is the soffset -- one scalar constant shared by every access of the window, no
-    // scalar arithmetic per access.  `coff` is the whole constant part of the address (a constant added to `voff`
-    // by the caller would overflow the immediate field and cost a vector add).  The range check sees
-    // voffset + immediate: a lane without a node (voffset = QP_OOB) stays wholly out of range.
-    // The lane offset is made opaque first (not volatile: equal ones still merge): the optimiser otherwise pushes
-    // the constant through the select that forms it (node ? t * 8 : QP_OOB) and keeps one precomputed vector
-    // register per accessed column live across the whole kernel.
-    static constexpr int IMM = 0xFFF;
-    static __device__ __forceinline__ int vopq(int v) {
-        asm("" : "+v"(v));
-        return v;
-    }
-    __device__ __forceinline__ double ldk(int voff, int coff) const {
-        cnt(voff, coff, 8.0);
-        return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, vopq(voff) + (coff & IMM), coff & ~IMM, 0));
-    }
-    __device__ __forceinline__ qp_u4 ld4k(int voff, int coff) const {
-        cnt(voff, coff, 16.0);
-        return __builtin_amdgcn_raw_buffer_load_b128(rs, vopq(voff) + (coff & IMM), coff & ~IMM, 0);
-    }
-    __device__ __forceinline__ void stk(int voff, int coff, double v) const {
-        cnt(voff, coff, 8.0);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(qp_u2, v), rs, vopq(voff) + (coff & IMM), coff & ~IMM, 0);
-    }
-};
-// keep a value opaque to the optimiser (volatile: re-derived where it is used, never hoisted)
-__device__ __forceinline__ int qp_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-// 1.0 if a == b else 0.0, opaque to the optimiser: selecting an array element by a runtime
-// index with this mask stays arithmetic (a compare/select chain is turned back into a
-// dynamically indexed private array, i.e. scratch memory)
-__device__ __forceinline__ double qp_mask(int a, int b) {
-    int m = a == b ? 1 : 0;
-    asm("" : "+v"(m));
-    return (double)m;
-}
-
-// One lane's repetition of a factor phase, decoded once per sweep (the offsets are stage-invariant)
-struct QPRep {
-    int L, R, B, O, G;   // LDS operand / base / output offsets; byte voffset of the global store
-    double b1, b2, acc;  // base multipliers (every stage, last stage only); 1 if the output accumulates
-};
-// lsink: LDS sink (outputs that go nowhere in LDS, and accumulating outputs, which live in registers
-// during the sweep); jnk: the junk slot of the stage block
-__device__ __forceinline__ QPRep qp_decode(const int (&d)[4], int one, int lsink, int jnk) {
-    QPRep q;
-    q.L = d[0] & 0x7FFF;
-    q.R = d[1] & 0x7FFF;
-    const int bk = d[3] >> 16;
-    q.B = bk ? (d[3] & 0x7FFF) : one;
-    q.b1 = bk == 1 ? 1.0 : 0.0;
-    q.b2 = bk == 2 ? 1.0 : 0.0;
-    const int O = d[2];
-    const bool on = O >= 0, acc = on && ((O >> 15) & 1);
-    q.O = (on && !acc) ? (O & 0x7FFF) : lsink;
-    q.acc = acc ? 1.0 : 0.0;
-    const int g = on ? (O >> 17) - 1 : -1;
-    q.G = (g >= 0 ? g : jnk) * 8;
-    return q;
-}
-
-template <int KK>
-__device__ __forceinline__ double qp_dot(const double* lds, int L, int R) {
-    const double* lp = lds + L;
-    const double* rp = lds + R;
-    double acc0 = 0.0, acc1 = 0.0;
-#pragma unroll
-    for (int k = 0; k < KK; ++k) {
-        if (k & 1) acc1 = fma(lp[k], rp[k], acc1); else acc0 = fma(lp[k], rp[k], acc0);
-    }
-    return acc0 + acc1;
-}
-
-// One element-parallel phase of the factor sweep: every lane evaluates its NREP repetitions
-// (out = base + sum_k L[k] R[k]), writes each to its LDS slot and its global column, and adds the
-// accumulating ones (M, xe: summed over the stages) into registers -- no LDS read-modify-write on the
-// sweep's chain.
-// (outputs [ALO, AHI) of the phase may accumulate: only the repetitions covering them keep a register sum)
-template <int KK, int NREP, int ALO = 0, int AHI = WAVE * NREP>
-__device__ __forceinline__ void qp_phase(double* lds, const QPRep (&d)[NREP], double blast, const QPBuf& wb, int fbo,
-                                         double (&areg)[NREP]) {
-    double val[NREP];
-#pragma unroll
-    for (int r = 0; r < NREP; ++r)
-        val[r] = fma(lds[d[r].B], d[r].b1 + blast * d[r].b2, qp_dot<KK>(lds, d[r].L, d[r].R));
-#pragma unroll
-    for (int r = 0; r < NREP; ++r) {
-        lds[d[r].O] = val[r];
-        if (WAVE * r < AHI && WAVE * r + WAVE > ALO) areg[r] = fma(d[r].acc, val[r], areg[r]);
-        wb.st(d[r].G, fbo, val[r]);
-    }
-}
-
-// Compact repetition (n = 12 classes): the base / accumulate flags packed in F (bits 0-1: base kind 0 none,
-// 1 every stage, 2 last stage; bit 2: accumulating output) instead of three doubles, and the accumulating
-// outputs keep their LDS target in O (written every stage, overwritten by the register sum after the
-// sweep; nothing reads V_M / V_XE during it).  20 repetitions x 6 instead of 11 registers at NX = 12.
-// Packed in three registers (round 4: the six-int form held 120 registers across the n = 12 sweep, which
-// spilled to scratch inside the stage loop): L | R << 16, B | O << 16, G | F << 16 (LDS offsets < 2^15
-// doubles, the global byte offset within a stage block < 2^16).
-struct QPRepC {
-    int LR, BO, GF;
-    __device__ __forceinline__ int L() const { return LR & 0xFFFF; }
-    __device__ __forceinline__ int R() const { return LR >> 16; }
-    __device__ __forceinline__ int B() const { return BO & 0xFFFF; }
-    __device__ __forceinline__ int O() const { return BO >> 16; }
-    __device__ __forceinline__ int G() const { return GF & 0xFFFF; }
-    __device__ __forceinline__ int F() const { return GF >> 16; }
-};
-__device__ __forceinline__ QPRepC qp_decode_c(const int (&d)[4], int one, int lsink, int jnk) {
-    QPRepC q;
-    const int L = d[0] & 0x7FFF, R = d[1] & 0x7FFF;
-    const int bk = d[3] >> 16;
-    const int B = bk ? (d[3] & 0x7FFF) : one;
-    const int O = d[2];
-    const bool on = O >= 0, acc = on && ((O >> 15) & 1);
-    const int Oo = on ? (O & 0x7FFF) : lsink;
-    const int g = on ? (O >> 17) - 1 : -1;
-    const int G = (g >= 0 ? g : jnk) * 8;
-    const int F = bk | (acc ? 4 : 0);
-    q.LR = L | (R << 16);
-    q.BO = B | (Oo << 16);
-    q.GF = G | (F << 16);
-    return q;
-}
-// as qp_phase; outputs [ALO, AHI) of the phase may accumulate (only those repetitions keep a register sum)
-template <int KK, int NREP, int ALO, int AHI>
-__device__ __forceinline__ void qp_phase_c(double* lds, const QPRepC* d, double blast, const QPBuf& wb,
-                                           int fbo, double (&areg)[NREP]) {
-    const QPRepC* q = d;
-    double val[NREP];
-#pragma unroll
-    for (int r = 0; r < NREP; ++r) {
-        const int bk = q[r].F() & 3;
-        const double bm = (bk == 1 ? 1.0 : 0.0) + blast * (bk == 2 ? 1.0 : 0.0);
-        val[r] = fma(lds[q[r].B()], bm, qp_dot<KK>(lds, q[r].L(), q[r].R()));
-    }
-#pragma unroll
-    for (int r = 0; r < NREP; ++r) {
-        lds[q[r].O()] = val[r];
-        if constexpr (true) {
-            if (WAVE * r < AHI && WAVE * r + WAVE > ALO) areg[r] = fma((q[r].F() & 4) ? 1.0 : 0.0, val[r], areg[r]);
-        }
-        wb.st(q[r].G(), fbo, val[r]);
-    }
-}
 
 // KC: the node count K at compile time (0: T.K at run time).  With KC set, every workspace offset (the column stride,
 // the packet and factor-block bases), the LDS offsets of the K-sized blocks and the chunk geometry are constants;
@@ -547,8 +63,8 @@ __device__ __forceinline__ void qp_phase_c(double* lds, const QPRepC* d, double 
 // written by one is valid for the other).  The host picks KC = T.K where it is compiled (qp_inst.hpp QPKSpec).
 template <class C, int KC = 0>
 __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
-    constexpr int NX = C::NX, NU = C::NU, NZ = C::NZ, NQ = C::NQ, NR = C::NR, NG = C::NG, NS = C::NS,
-                  NO = C::NO, NC = C::NC, NB = C::NB, PKT = C::PKT, NV = C::NV, NVA = C::NVA;
+    constexpr int NX = C::L.NX, NU = C::L.NU, NZ = C::L.NZ, NQ = C::L.NQ, NR = C::L.NR, NG = C::L.NG, NS = C::L.NS,
+                  NO = C::L.NO, NC = C::L.NC, NB = C::L.NB, PKT = C::L.PKT, NV = C::L.NV, NVA = C::L.NVA;
     constexpr int NGA = NG > 0 ? NG : 1, NSA = NS > 0 ? NS : 1, NBA = NB > 0 ? NB : 1;
     // solve-chain prefetch depth: two stages for the n = 12 classes (4 x 12 held doubles would spill)
     constexpr int CPF = NX > 8 ? 2 : QP_CPF;
@@ -613,17 +129,17 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     const bool fixed_u = act && (t == K - 1) && T.fix_last_input;
     const bool tsoft = soft_fin && act && (t == K - 1);
     const double wfs = tsoft ? T.w_final * iosc : 0.0;
-    const double* disc = a.disc + agent * (long long)(K - 1) * C::DSTR;
+    const double* disc = a.disc + agent * (long long)(K - 1) * C::L.DSTR;
     double* ws = a.ws + agent * a.ws_agent;
     QPBuf wb;
     // num_records = the agent's workspace: the lanes without a node address QP_OOB (reads 0, stores dropped)
     wb.rs = __builtin_amdgcn_make_buffer_rsrc(ws, (short)0, (int)(a.ws_agent * 8), 0x00020000);
     const int colb = K * 8;      // bytes per workspace column (one double per node)
     const int vt = act ? t * 8 : QP_OOB;  // this lane's element of a stage-minor column
-    const int PKB = qp_even(C::NCOL * K) * 8;      // byte offset of the packets [t][GPK] (16-byte aligned)
-    const int FBB = PKB + qp_even(K * C::GPK) * 8;  // byte offset of the factor output blocks [t][FBS] (likewise)
-    const int vpk = act ? t * C::GPK * 8 : QP_OOB;
-    const int vfb = act ? t * C::FBS * 8 : QP_OOB;
+    const int PKB = qp_even(C::L.NCOL * K) * 8;      // byte offset of the packets [t][GPK] (16-byte aligned)
+    const int FBB = PKB + qp_even(K * C::L.GPK) * 8;  // byte offset of the factor output blocks [t][FBS] (likewise)
+    const int vpk = act ? t * C::L.GPK * 8 : QP_OOB;
+    const int vfb = act ? t * C::L.FBS * 8 : QP_OOB;
     // Loads go through `vcur` / `vpcur`, this lane's offsets re-derived (opaquely) at the start of every
     // phase: a load in one phase is then never merged with the same load of an earlier phase, which
     // would keep the value live in registers across the sweeps in between.  The lane-parallel passes
@@ -689,17 +205,17 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     };
     auto pst = [&](int e, double v) __attribute__((always_inline)) { wst(vpk, PKB + e * 8, v); };
 
-    constexpr int V_M = C::L_M, V_PI0 = C::L_PI0, V_XE = C::L_XE, V_XI0 = C::L_XI0, V_R2F = C::L_R2F,
-                  V_YI = C::L_YI, V_YF = C::L_YF, V_DYI = C::L_DYI, V_DYF = C::L_DYF, V_PIV = C::L_PIV,
-                  V_ONE = C::L_ONE, V_FLAG = C::L_FLAG, V_ST = C::L_ST, V_S = C::L_S, V_L = C::L_L;
+    constexpr int V_M = C::L.L_M, V_PI0 = C::L.L_PI0, V_XE = C::L.L_XE, V_XI0 = C::L.L_XI0, V_R2F = C::L.L_R2F,
+                  V_YI = C::L.L_YI, V_YF = C::L.L_YF, V_DYI = C::L.L_DYI, V_DYF = C::L.L_DYF, V_PIV = C::L.L_PIV,
+                  V_ONE = C::L.L_ONE, V_FLAG = C::L.L_FLAG, V_ST = C::L.L_ST, V_S = C::L.L_S, V_L = C::L.L_L;
     // STF: 1 once a stage of the last factor sweep kept a stiff facet (the solve and the Newton passes skip the
     // stage-system terms otherwise: every stage's slots are empty then)
-    constexpr int V_SANY = C::L_FLAG + 1;
+    constexpr int V_SANY = C::L.L_FLAG + 1;
     auto stf_any = [&]() __attribute__((always_inline)) -> bool {
         return __builtin_amdgcn_readfirstlane((int)(lds[V_SANY] != 0.0)) != 0;
     };
-    const int V_G = C::L_VAR, V_CH = V_G + K * NX, V_PHI = V_CH + (K + 1) * NX;
-    // chunked chains (C::CHK): transitions t = 0..K-2 in chunks of CL; lane = 8 ch + ce carries element ce of
+    const int V_G = C::L.L_VAR, V_CH = V_G + K * NX, V_PHI = V_CH + (K + 1) * NX;
+    // chunked chains (C::L.CHK): transitions t = 0..K-2 in chunks of CL; lane = 8 ch + ce carries element ce of
     // chunk ch, whose transitions are [cs0, cs1)
     const int KS = K - 1, CL = (KS + QP_NCH - 1) / QP_NCH, NCH = (KS + CL - 1) / CL;
     // (a phase re-derives these from qp_opaque(lane) through chunk_coords(): the address arithmetic is then
@@ -750,15 +266,15 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         double Cp[NX * NU];
 #pragma unroll
         for (int e = 0; e < NX * NU; ++e)
-            Cp[e] = (act && t > 0) ? disc[(long long)(t - 1) * C::DSTR + NX * NX + NX * NU + e] : 0.0;
+            Cp[e] = (act && t > 0) ? disc[(long long)(t - 1) * C::L.DSTR + NX * NX + NX * NU + e] : 0.0;
         // transposed disc (zero for t >= K-1), Bt = B + A C_{t-1}, the constant part of the packets
         double Ad[NX * NX], Bd[NX * NU];
         const bool dyn = t < K - 1;
-        for (int e = 0; e < C::DSTR; ++e) cst(C::C_DT + e, dyn ? disc[(long long)t * C::DSTR + e] : 0.0);
+        for (int e = 0; e < C::L.DSTR; ++e) cst(C::L.C_DT + e, dyn ? disc[(long long)t * C::L.DSTR + e] : 0.0);
 #pragma unroll
-        for (int e = 0; e < NX * NX; ++e) Ad[e] = dyn ? disc[(long long)t * C::DSTR + e] : 0.0;
+        for (int e = 0; e < NX * NX; ++e) Ad[e] = dyn ? disc[(long long)t * C::L.DSTR + e] : 0.0;
 #pragma unroll
-        for (int e = 0; e < NX * NU; ++e) Bd[e] = dyn ? disc[(long long)t * C::DSTR + NX * NX + e] : 0.0;
+        for (int e = 0; e < NX * NU; ++e) Bd[e] = dyn ? disc[(long long)t * C::L.DSTR + NX * NX + e] : 0.0;
         if (act) {
 #pragma unroll
             for (int i = 0; i < NX; ++i)
@@ -767,17 +283,17 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     double v = Bd[j * NX + i];
 #pragma unroll
                     for (int k = 0; k < NX; ++k) v = fma(Ad[k * NX + i], Cp[j * NX + k], v);
-                    cst(C::C_BT + i * NU + j, v);
-                    pst(C::gBT + j * NX + i, v);
-                    if constexpr (C::DPK) pst(C::P_BTR + i * NU + j, v);
+                    cst(C::L.C_BT + i * NU + j, v);
+                    pst(C::L.gBT + j * NX + i, v);
+                    if constexpr (C::L.DPK) pst(C::L.P_BTR + i * NU + j, v);
                 }
 #pragma unroll
             for (int e = 0; e < NX * NX; ++e) {
-                pst(C::gA + e, Ad[e]);
-                if constexpr (C::DPK) pst(C::P_Q + e, 0.0);
+                pst(C::L.gA + e, Ad[e]);
+                if constexpr (C::L.DPK) pst(C::L.P_Q + e, 0.0);
             }
 #pragma unroll
-            for (int e = 0; e < NX * NU; ++e) pst(C::gC + e, Cp[e]);
+            for (int e = 0; e < NX * NU; ++e) pst(C::L.gC + e, Cp[e]);
         }
         // soft rows: obstacle linearisations (single_integrator_model.py:113-126) from Xref, then
         // the caller's collision rows (dist_scvx_3d.py:93-107)
@@ -802,8 +318,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 }
             }
 #pragma unroll
-            for (int i = 0; i < 3; ++i) cst(C::C_SOFT + o * 4 + i, d[i]);
-            cst(C::C_SOFT + o * 4 + 3, bo);
+            for (int i = 0; i < 3; ++i) cst(C::L.C_SOFT + o * 4 + i, d[i]);
+            cst(C::L.C_SOFT + o * 4 + 3, bo);
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -814,25 +330,25 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 g[3] = src[pd];
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) cst(C::C_SOFT + (NO + c) * 4 + i, g[i]);
+            for (int i = 0; i < 4; ++i) cst(C::L.C_SOFT + (NO + c) * 4 + i, g[i]);
         }
         // initial node state: z = (xbar, ubar), y = 0, slack groups 0
 #pragma unroll
-        for (int j = 0; j < NU; ++j) cst(C::C_UB + j, act ? a.Uref[(agent * K + t) * NU + j] : 0.0);
+        for (int j = 0; j < NU; ++j) cst(C::L.C_UB + j, act ? a.Uref[(agent * K + t) * NU + j] : 0.0);
         if (warm) {   // the last solve's primal / dual state stays in place; its y_init / y_fin to LDS
-            if (lane < 2 * NX) lds[V_YI + lane] = wld(vt, C::C_WY * colb);   // (V_YF = V_YI + NX)
+            if (lane < 2 * NX) lds[V_YI + lane] = wld(vt, C::L.C_WY * colb);   // (V_YF = V_YI + NX)
         } else {
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
-                cst(C::C_Z + i, act ? a.Xref[(agent * K + t) * NX + i] : 0.0);
-                cst(C::C_Y + i, 0.0);
+                cst(C::L.C_Z + i, act ? a.Xref[(agent * K + t) * NX + i] : 0.0);
+                cst(C::L.C_Y + i, 0.0);
             }
 #pragma unroll
-            for (int j = 0; j < NU; ++j) cst(C::C_Z + NX + j, act ? a.Uref[(agent * K + t) * NU + j] : 0.0);
+            for (int j = 0; j < NU; ++j) cst(C::L.C_Z + NX + j, act ? a.Uref[(agent * K + t) * NU + j] : 0.0);
 #pragma unroll
-            for (int g = 0; g < NG; ++g) cst(C::C_AV + g, 0.0);
+            for (int g = 0; g < NG; ++g) cst(C::L.C_AV + g, 0.0);
 #pragma unroll
-            for (int i = 0; i < NV; ++i) { cst(C::C_VN + i, 0.0); cst(C::C_VE + i, 0.0); }
+            for (int i = 0; i < NV; ++i) { cst(C::L.C_VN + i, 0.0); cst(C::L.C_VE + i, 0.0); }
             if (lane < NX) { lds[V_YI + lane] = 0.0; lds[V_YF + lane] = 0.0; }
         }
         if (lane == 0) lds[V_ONE] = 1.0;
@@ -841,7 +357,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     // C_{t-1} (column-major as disc) of this node, from the transposed disc of node t-1 (the lane below)
     auto load_cp = [&](double* Cp) __attribute__((always_inline)) {
 #pragma unroll
-        for (int e = 0; e < NX * NU; ++e) Cp[e] = wld(vcur - 8, (C::C_DT + NX * NX + NX * NU + e) * colb);
+        for (int e = 0; e < NX * NU; ++e) Cp[e] = wld(vcur - 8, (C::L.C_DT + NX * NX + NX * NU + e) * colb);
         hold(Cp, NX * NU);
 #pragma unroll
         for (int e = 0; e < NX * NU; ++e) Cp[e] = (t > 0) ? Cp[e] : 0.0;
@@ -858,30 +374,30 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         constexpr int R1 = (E1 + WAVE - 1) / WAVE, R2 = (E2 + WAVE - 1) / WAVE, R4 = (E4 + WAVE - 1) / WAVE;
         int d1[R1][4], d2[R2][4], d4[R4][4];
         {
-            const int sink = C::F_SINK;
+            const int sink = C::L.F_SINK;
             const int ln = qp_opaque(lane);  // volatile: keeps the descriptors inside the IPM loop
 #pragma unroll
             for (int rep = 0; rep < R1; ++rep) {
                 int o = ln + rep * WAVE, L = 0, R = 0, O = -1, B = 0;
                 if (o < NX * NX) {  // T1 = P' A  -> T1 column-major
                     const int i = o / NX, j = o % NX;
-                    L = qp_dpk(C::F_PP + i * NX, 0); R = qp_dpk(C::P_A + j * NX, 1); O = C::F_T1 + j * NX + i;
+                    L = C::L.F_PP + i * NX; R = C::L.P_A + j * NX; O = C::L.F_T1 + j * NX + i;
                 } else if ((o -= NX * NX) < NX * NU) {  // T2 = P' Bt -> column-major
                     const int i = o / NU, j = o % NU;
-                    L = qp_dpk(C::F_PP + i * NX, 0); R = qp_dpk(C::P_BT + j * NX, 1); O = C::F_T2 + j * NX + i;
+                    L = C::L.F_PP + i * NX; R = C::L.P_BT + j * NX; O = C::L.F_T2 + j * NX + i;
                 } else if ((o -= NX * NU) < NX * NX) {  // W1 = A' Pi'   (I at the last stage)
                     const int i = o / NX, j = o % NX;
-                    L = qp_dpk(C::P_A + i * NX, 1); R = qp_dpk(C::F_PIP + j * NX, 0); O = C::F_W1 + o;
+                    L = C::L.P_A + i * NX; R = C::L.F_PIP + j * NX; O = C::L.F_W1 + o;
                     B = (i == j) ? (V_ONE | (2 << 16)) : 0;
                 } else if ((o -= NX * NX) < NU * NX) {  // W2 = Bt' Pi' -> column-major (C_{K-2}' at the last stage)
                     const int i = o / NX, j = o % NX;
-                    L = qp_dpk(C::P_BT + i * NX, 1); R = qp_dpk(C::F_PIP + j * NX, 0);
-                    O = (C::F_W2 + j * NU + i) | ((C::B_W2 + o + 1) << 17);
-                    B = (C::P_C + i * NX + j) | (1 << 15) | (2 << 16);
+                    L = C::L.P_BT + i * NX; R = C::L.F_PIP + j * NX;
+                    O = (C::L.F_W2 + j * NU + i) | ((C::L.B_W2 + o + 1) << 17);
+                    B = (C::L.P_C + i * NX + j) | (1 << 15) | (2 << 16);
                 } else if ((o -= NU * NX) < NX) {  // u = P' e  (global only)
-                    L = qp_dpk(C::F_PP + o * NX, 0); R = qp_dpk(C::P_E, 1); O = sink | ((C::B_U + o + 1) << 17);
+                    L = C::L.F_PP + o * NX; R = C::L.P_E; O = sink | ((C::L.B_U + o + 1) << 17);
                 } else if ((o -= NX) < NX) {  // xe += Pi'' e
-                    L = qp_dpk(C::F_PIP + o * NX, 0); R = qp_dpk(C::P_E, 1); O = (V_XE + o) | (1 << 15);
+                    L = C::L.F_PIP + o * NX; R = C::L.P_E; O = (V_XE + o) | (1 << 15);
                 }
                 d1[rep][0] = L; d1[rep][1] = R; d1[rep][2] = O; d1[rep][3] = B;
             }
@@ -890,16 +406,16 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 int o = ln + rep * WAVE, L = 0, R = 0, O = -1, B = 0;
                 if (o < NX * NX) {  // Qh = Q + A' T1 (symmetric: (min, max) element for both halves)
                     const int i = o / NX, j = o % NX, p = i < j ? i : j, q = i < j ? j : i;
-                    L = qp_dpk(C::P_A + p * NX, 1); R = qp_dpk(C::F_T1 + q * NX, 0); O = C::F_QH + o;
-                    B = (C::P_Q + p * NX + q) | (1 << 15) | (1 << 16);
+                    L = C::L.P_A + p * NX; R = C::L.F_T1 + q * NX; O = C::L.F_QH + o;
+                    B = (C::L.P_Q + p * NX + q) | (1 << 15) | (1 << 16);
                 } else if ((o -= NX * NX) < NU * NX) {  // Sh = S' + Bt' T1 -> column-major
                     const int i = o / NX, j = o % NX;
-                    L = qp_dpk(C::P_BT + i * NX, 1); R = qp_dpk(C::F_T1 + j * NX, 0); O = C::F_SH + j * NU + i;
-                    B = (C::P_S + j * NU + i) | (1 << 15) | (1 << 16);
+                    L = C::L.P_BT + i * NX; R = C::L.F_T1 + j * NX; O = C::L.F_SH + j * NU + i;
+                    B = (C::L.P_S + j * NU + i) | (1 << 15) | (1 << 16);
                 } else if ((o -= NU * NX) < NU * NU) {  // Rh = R + Bt' T2
                     const int i = o / NU, j = o % NU, p = i < j ? i : j, q = i < j ? j : i;
-                    L = qp_dpk(C::P_BT + p * NX, 1); R = qp_dpk(C::F_T2 + q * NX, 0); O = C::F_RH + o;
-                    B = (C::P_R + p * NU + q) | (1 << 15) | (1 << 16);
+                    L = C::L.P_BT + p * NX; R = C::L.F_T2 + q * NX; O = C::L.F_RH + o;
+                    B = (C::L.P_R + p * NU + q) | (1 << 15) | (1 << 16);
                 }
                 d2[rep][0] = L; d2[rep][1] = R; d2[rep][2] = O; d2[rep][3] = B;
             }
@@ -908,20 +424,20 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 int o = ln + rep * WAVE, L = 0, R = 0, O = -1, B = 0;
                 if (o < NX * NX) {  // P = Qh + Sh' K (symmetric)
                     const int i = o / NX, j = o % NX, p = i < j ? i : j, q = i < j ? j : i;
-                    L = qp_dpk(C::F_SH + p * NU, 0); R = qp_dpk(C::F_KK + q * NU, 0);
-                    O = (C::F_PP + o) | ((C::B_P + o + 1) << 17); B = (C::F_QH + p * NX + q) | (1 << 16);
+                    L = C::L.F_SH + p * NU; R = C::L.F_KK + q * NU;
+                    O = (C::L.F_PP + o) | ((C::L.B_P + o + 1) << 17); B = (C::L.F_QH + p * NX + q) | (1 << 16);
                 } else if ((o -= NX * NX) < NX * NX) {  // Pi = W1 + Sh' kappa -> Pi' column-major
                     const int i = o / NX, j = o % NX;
-                    L = qp_dpk(C::F_SH + i * NU, 0); R = qp_dpk(C::F_KK + (NX + j) * NU, 0);
-                    O = (C::F_PIP + j * NX + i) | ((C::B_PI + o + 1) << 17); B = (C::F_W1 + o) | (1 << 16);
+                    L = C::L.F_SH + i * NU; R = C::L.F_KK + (NX + j) * NU;
+                    O = (C::L.F_PIP + j * NX + i) | ((C::L.B_PI + o + 1) << 17); B = (C::L.F_W1 + o) | (1 << 16);
                 } else if ((o -= NX * NX) < NX * NX) {  // M += W2' kappa (symmetric)
                     const int i = o / NX, j = o % NX, p = i < j ? i : j, q = i < j ? j : i;
-                    L = qp_dpk(C::F_W2 + p * NU, 0); R = qp_dpk(C::F_KK + (NX + q) * NU, 0); O = (V_M + o) | (1 << 15);
+                    L = C::L.F_W2 + p * NU; R = C::L.F_KK + (NX + q) * NU; O = (V_M + o) | (1 << 15);
                 } else if ((o -= NX * NX) < NX * NX) {  // Acl = A + Bt K  -> global (+ LDS column-major for VC)
                     const int i = o / NX, j = o % NX;
-                    L = qp_dpk(C::P_BTR + i * NU, 1); R = qp_dpk(C::F_KK + j * NU, 0);
-                    O = (C::NV > 0 ? C::F_ACLC + j * NX + i : sink) | ((C::B_ACL + o + 1) << 17);
-                    B = (C::P_A + j * NX + i) | (1 << 15) | (1 << 16);
+                    L = C::L.P_BTR + i * NU; R = C::L.F_KK + j * NU;
+                    O = (C::L.NV > 0 ? C::L.F_ACLC + j * NX + i : sink) | ((C::L.B_ACL + o + 1) << 17);
+                    B = (C::L.P_A + j * NX + i) | (1 << 15) | (1 << 16);
                 }
                 d4[rep][0] = L; d4[rep][1] = R; d4[rep][2] = O; d4[rep][3] = B;
             }
@@ -934,8 +450,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         // drained the packet prefetches in flight: ~100 serialised memory round trips per stage.
         constexpr bool CMP = NX > 8;
         constexpr int RT = R1 + R2 + R4;
-        static_assert(!CMP || RT == qp_nrep(NX, NU), "descriptor table size (qp_dtab, the host's workspace size)");
-        const int DTB = FBB + K * C::FBS * 8;   // byte offset of the descriptor table [rep][lane] x 16 B
+        static_assert(!CMP || RT == C::L.NREP, "descriptor table size (QPLay::dtab_doubles, the host's workspace size)");
+        const int DTB = FBB + K * C::L.FBS * 8;   // byte offset of the descriptor table [rep][lane] x 16 B
         QPRep q1[CMP ? 1 : R1], q2[CMP ? 1 : R2], q4[CMP ? 1 : R4];
         double a1[R1], a2[R2], a4[R4];
         // virtual control: the M contributions -Pi'' G^-1 Pi' of every stage (registers, like a4)
@@ -956,23 +472,23 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         };
 #pragma unroll
         for (int r = 0; r < R1; ++r) {
-            if constexpr (CMP) tab_st(r, qp_decode_c(d1[r], V_ONE, C::F_SINK, C::B_JNK));
-            else q1[r] = qp_decode(d1[r], V_ONE, C::F_SINK, C::B_JNK);
+            if constexpr (CMP) tab_st(r, qp_decode_c(d1[r], V_ONE, C::L.F_SINK, C::L.B_JNK));
+            else q1[r] = qp_decode(d1[r], V_ONE, C::L.F_SINK, C::L.B_JNK);
             a1[r] = 0.0;
         }
 #pragma unroll
         for (int r = 0; r < R2; ++r) {
-            if constexpr (CMP) tab_st(R1 + r, qp_decode_c(d2[r], V_ONE, C::F_SINK, C::B_JNK));
-            else q2[r] = qp_decode(d2[r], V_ONE, C::F_SINK, C::B_JNK);
+            if constexpr (CMP) tab_st(R1 + r, qp_decode_c(d2[r], V_ONE, C::L.F_SINK, C::L.B_JNK));
+            else q2[r] = qp_decode(d2[r], V_ONE, C::L.F_SINK, C::L.B_JNK);
             a2[r] = 0.0;
         }
 #pragma unroll
         for (int r = 0; r < R4; ++r) {
-            if constexpr (CMP) tab_st(R1 + R2 + r, qp_decode_c(d4[r], V_ONE, C::F_SINK, C::B_JNK));
-            else q4[r] = qp_decode(d4[r], V_ONE, C::F_SINK, C::B_JNK);
+            if constexpr (CMP) tab_st(R1 + R2 + r, qp_decode_c(d4[r], V_ONE, C::L.F_SINK, C::L.B_JNK));
+            else q4[r] = qp_decode(d4[r], V_ONE, C::L.F_SINK, C::L.B_JNK);
             a4[r] = 0.0;
         }
-        for (int e = lane; e < NX * NX; e += WAVE) { lds[C::F_PP + e] = 0.0; lds[C::F_PIP + e] = 0.0; lds[V_M + e] = 0.0; }
+        for (int e = lane; e < NX * NX; e += WAVE) { lds[C::L.F_PP + e] = 0.0; lds[C::L.F_PIP + e] = 0.0; lds[V_M + e] = 0.0; }
         if (lane < NX) lds[V_XE + lane] = 0.0;
         if (lane == 0) { lds[V_FLAG] = 0.0; lds[V_SANY] = 0.0; }
         __syncthreads();  // the node phase wrote the packets (global) from other lanes
@@ -985,23 +501,23 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         // n <= 8: lane's global packet element per prefetch slot (structural zeros read past the end: 0);
         // n = 12 (dense packet): lane l loads elements l + 64 k (the padding lanes of the last slot read the next
         // packet / factor block and store to the sink) -- no table held across the sweep
-        int pfo[C::DPK ? 1 : PFN];
-        if constexpr (!C::DPK) {
+        int pfo[C::L.DPK ? 1 : PFN];
+        if constexpr (!C::L.DPK) {
 #pragma unroll
             for (int k = 0; k < PFN; ++k) {
                 const int e = qp_opaque(lane) + WAVE * k;
-                const int g = e < PKT ? C::gsrc(e) : -1;  // padding lanes read 0 (stored to the sink)
+                const int g = e < PKT ? qp_gsrc<C::L>(e) : -1;  // padding lanes read 0 (stored to the sink)
                 pfo[k] = g >= 0 ? g * 8 : QP_OOB;
             }
         }
         auto pf_load = [&](int ts, double* b) __attribute__((always_inline)) {
-            if constexpr (C::DPK) {
+            if constexpr (C::L.DPK) {
                 const int vo = qp_opaque(lane) * 8;
 #pragma unroll
-                for (int k = 0; k < PFN; ++k) b[k] = wb.ld(vo, PKB + (ts > 0 ? ts : 0) * C::GPK * 8 + k * WAVE * 8);
+                for (int k = 0; k < PFN; ++k) b[k] = wb.ld(vo, PKB + (ts > 0 ? ts : 0) * C::L.GPK * 8 + k * WAVE * 8);
             } else {
 #pragma unroll
-                for (int k = 0; k < PFN; ++k) b[k] = wb.ld(pfo[k], PKB + (ts > 0 ? ts : 0) * C::GPK * 8);
+                for (int k = 0; k < PFN; ++k) b[k] = wb.ld(pfo[k], PKB + (ts > 0 ? ts : 0) * C::L.GPK * 8);
             }
         };
         auto pf_store = [&](int ts, const double* b) __attribute__((always_inline)) {
@@ -1009,7 +525,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
             for (int k = 0; k < PFN; ++k) {
                 const int e = sl + WAVE * k;
-                lds[e < PKT ? C::F_RING + e : C::F_SINK] = b[k];
+                lds[e < PKT ? C::L.F_RING + e : C::L.F_SINK] = b[k];
             }
         };
         if constexpr (FPD == 3) {
@@ -1032,7 +548,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         auto stage = [&](auto lastc, int ts, double* nb, const double* cb) __attribute__((always_inline)) {
             constexpr bool last = decltype(lastc)::value;
             const double blast = last ? 1.0 : 0.0;
-            const int fbo = FBB + ts * C::FBS * 8;  // byte offset of this stage's output block (uniform)
+            const int fbo = FBB + ts * C::L.FBS * 8;  // byte offset of this stage's output block (uniform)
             // n = 12: the lane index re-derived per stage: lane-dependent addresses and masks are rebuilt in the
             // stage, not hoisted out of the IPM loop and held (spilled) across it (n <= 8: hoisted, in registers)
             const int sl = NX > 8 ? qp_opaque(lane) : lane;
@@ -1046,16 +562,16 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             // STF: the node's largest facet weight if it is a stiff candidate (assemble), else 0 -- read before the
             // phases, off phase 3's chain
             double dfmr = 0.0;
-            if constexpr (C::STF) dfmr = lds[C::F_RING + C::P_FD + C::NTR + 1 + C::NFO];
-            if constexpr (C::NV > 0) {
+            if constexpr (C::L.STF) dfmr = lds[C::L.F_RING + C::L.P_FD + C::L.NTR + 1 + C::L.NFO];
+            if constexpr (C::L.NV > 0) {
                 // ---- phase 0 (virtual control nu_ts): G = diag(D) + P', then [G^-1 Pi' | G^-1 | G^-1 P'] by
                 // Gauss-Jordan without pivoting (G is SPD): lane c < 4 NX owns column c of [G | Pi' | I | P'];
                 // the pivot column is broadcast by readlane (no LDS round trip per pivot).  At the last stage
                 // P' = Pi' = 0 and D = 1 (assemble), so nothing changes there.
                 const int c = sl < 4 * NX ? sl : 0, blk = c / NX, cc = c - blk * NX;
-                const int base = (blk == 1 ? C::F_PIP : C::F_PP) + cc * NX;   // P' symmetric: row = column
+                const int base = (blk == 1 ? C::L.F_PIP : C::L.F_PP) + cc * NX;   // P' symmetric: row = column
                 const double keep = blk == 2 ? 0.0 : 1.0;
-                const double dcc = lds[C::F_RING + C::P_D + cc];
+                const double dcc = lds[C::L.F_RING + C::L.P_D + cc];
                 const double diag = (blk == 2 ? 1.0 : 0.0) + (blk == 0 ? dcc : 0.0);
                 double col[NX];
 #pragma unroll
@@ -1073,33 +589,33 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 // outputs: G^-1 Pi' -> F_YPI / B_YPI, Z = G^-1 D (row-major) -> F_Z, G^-1 -> B_GI,
                 // G^-1 P' -> F_YP / B_YP (column-major)
                 const bool own = sl >= NX && sl < 4 * NX;
-                const int gcol = blk == 1 ? C::B_YPI : (blk == 2 ? C::B_GI : C::B_YP);
+                const int gcol = blk == 1 ? C::L.B_YPI : (blk == 2 ? C::L.B_GI : C::L.B_YP);
 #pragma unroll
                 for (int i = 0; i < NX; ++i) {
-                    const int lo = !own ? C::F_SINK + i
-                                        : (blk == 1 ? C::F_YPI + cc * NX + i
-                                                    : (blk == 2 ? C::F_Z + i * NX + cc : C::F_YP + cc * NX + i));
+                    const int lo = !own ? C::L.F_SINK + i
+                                        : (blk == 1 ? C::L.F_YPI + cc * NX + i
+                                                    : (blk == 2 ? C::L.F_Z + i * NX + cc : C::L.F_YP + cc * NX + i));
                     lds[lo] = blk == 2 ? col[i] * dcc : col[i];
-                    wb.st((own ? gcol + cc * NX + i : C::B_JNK) * 8, fbo, col[i]);
+                    wb.st((own ? gcol + cc * NX + i : C::L.B_JNK) * 8, fbo, col[i]);
                 }
                 wsync();
                 // P~ = D G^-1 P' (symmetrised) -> F_PP; M -= Pi'' G^-1 Pi' (registers)
 #pragma unroll
                 for (int r = 0; r < R0; ++r) {
                     const int o = sl + r * WAVE, oo = o < NX * NX ? o : 0, i = oo / NX, j = oo - i * NX;
-                    const double pt = 0.5 * (lds[C::F_RING + C::P_D + i] * lds[C::F_YP + j * NX + i] +
-                                             lds[C::F_RING + C::P_D + j] * lds[C::F_YP + i * NX + j]);
-                    const double mv = qp_dot<NX>(lds, C::F_PIP + i * NX, C::F_YPI + j * NX);
+                    const double pt = 0.5 * (lds[C::L.F_RING + C::L.P_D + i] * lds[C::L.F_YP + j * NX + i] +
+                                             lds[C::L.F_RING + C::L.P_D + j] * lds[C::L.F_YP + i * NX + j]);
+                    const double mv = qp_dot<NX>(lds, C::L.F_PIP + i * NX, C::L.F_YPI + j * NX);
                     amv[r] -= o < NX * NX ? mv : 0.0;
-                    lds[o < NX * NX ? C::F_PP + o : C::F_SINK] = pt;
+                    lds[o < NX * NX ? C::L.F_PP + o : C::L.F_SINK] = pt;
                 }
                 wsync();
                 // Pi~ = D G^-1 Pi' -> F_PIP (column-major: element o = j NX + i is row i)
 #pragma unroll
                 for (int r = 0; r < R0; ++r) {
                     const int o = sl + r * WAVE, oo = o < NX * NX ? o : 0;
-                    const double v = lds[C::F_RING + C::P_D + (oo % NX)] * lds[C::F_YPI + oo];
-                    lds[o < NX * NX ? C::F_PIP + o : C::F_SINK] = v;
+                    const double v = lds[C::L.F_RING + C::L.P_D + (oo % NX)] * lds[C::L.F_YPI + oo];
+                    lds[o < NX * NX ? C::L.F_PIP + o : C::L.F_SINK] = v;
                 }
                 wsync();
             }
@@ -1122,10 +638,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 // classes without facets), one scalar branch between them
                 auto ph3 = [&](auto candc) __attribute__((always_inline)) {
                 constexpr bool CAND = decltype(candc)::value;
-                constexpr int PM = C::PM, PMA = C::PMA;
+                constexpr int PM = C::L.PM, PMA = C::L.PMA;
                 double Lm[NU * NU], dinv[NU];
 #pragma unroll
-                for (int e = 0; e < NU * NU; ++e) Lm[e] = lds[C::F_RH + e];
+                for (int e = 0; e < NU * NU; ++e) Lm[e] = lds[C::L.F_RH + e];
                 // stiff trust-region facets (STF): Rhat arrives without the facets.  Those whose weight exceeds
                 // QP_STIFF x its largest diagonal stay explicit when there are at most m-1 of them and no two are
                 // opposite (a face or an edge of the L1 ball: they leave a complement whose small curvature the fold
@@ -1137,8 +653,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
                 for (int i = 0; i < PMA; ++i) { sfi[i] = -1; sfd[i] = 1.0; }
                 bool stg = false;   // this stage keeps a stiff facet (uniform: a scalar branch)
-                if constexpr (C::STF && CAND) {
-                    constexpr int NTR = C::NTR, FS = C::F_RING + C::P_FD + NTR;
+                if constexpr (C::L.STF && CAND) {
+                    constexpr int NTR = C::L.NTR, FS = C::L.F_RING + C::L.P_FD + NTR;
                     // a candidate node (assemble: its facets left out of R, dfm > 0); every lane reads the same packet
                     // words, and readfirstlane makes the branches scalar (not predicated)
                     {
@@ -1165,7 +681,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                         int cnt = 0;
 #pragma unroll
                         for (int f = 0; f < NTR; ++f) {
-                            Df[f] = lds[C::F_RING + C::P_FD + f];
+                            Df[f] = lds[C::L.F_RING + C::L.P_FD + f];
                             const bool above = Df[f] > thr;
 #pragma unroll
                             for (int i = 0; i < PM; ++i) {
@@ -1187,7 +703,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                         }
                         if (use) {   // Rhat + the non-stiff facets, one at a time (the twin's order)
 #pragma unroll
-                            for (int e = 0; e < NU * NU; ++e) Lm[e] = lds[C::F_RH + e];
+                            for (int e = 0; e < NU * NU; ++e) Lm[e] = lds[C::L.F_RH + e];
 #pragma unroll
                             for (int f = 0; f < NTR; ++f) {
                                 bool st = false;
@@ -1267,7 +783,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 for (int e = 0; e < NU * PMA; ++e) Wm[e] = 0.0;
 #pragma unroll
                 for (int e = 0; e < PMA * PMA; ++e) Ci[e] = (e / PMA == e % PMA) ? 1.0 : 0.0;
-                if (C::STF && CAND && stg) {
+                if (C::L.STF && CAND && stg) {
 #pragma unroll
                     for (int i = 0; i < PM; ++i) {
                         double w[NU];
@@ -1314,12 +830,12 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                                    " | Rhat %.6e %.6e %.6e %.6e %.6e %.6e %.6e %.6e %.6e | dinv %.6e %.6e %.6e | L %.6e %.6e %.6e\n",
                                    agent, ts, Lm0[0], Lm0[1 % (NU * NU)], Lm0[2 % (NU * NU)], Lm0[3 % (NU * NU)],
                                    Lm0[4 % (NU * NU)], Lm0[5 % (NU * NU)], Lm0[6 % (NU * NU)], Lm0[7 % (NU * NU)],
-                                   Lm0[8 % (NU * NU)], lds[C::F_RH + 0], lds[C::F_RH + 1], lds[C::F_RH + 2],
-                                   lds[C::F_RH + 3], lds[C::F_RH + 4 % (NU * NU)], lds[C::F_RH + 5 % (NU * NU)],
-                                   lds[C::F_RH + 6 % (NU * NU)], lds[C::F_RH + 7 % (NU * NU)], lds[C::F_RH + 8 % (NU * NU)], dinv[0],
+                                   Lm0[8 % (NU * NU)], lds[C::L.F_RH + 0], lds[C::L.F_RH + 1], lds[C::L.F_RH + 2],
+                                   lds[C::L.F_RH + 3], lds[C::L.F_RH + 4 % (NU * NU)], lds[C::L.F_RH + 5 % (NU * NU)],
+                                   lds[C::L.F_RH + 6 % (NU * NU)], lds[C::L.F_RH + 7 % (NU * NU)], lds[C::L.F_RH + 8 % (NU * NU)], dinv[0],
                                    dinv[1 % NU], dinv[2 % NU], Lm[3 % (NU * NU)], Lm[6 % (NU * NU)], Lm[7 % (NU * NU)]);
                             double Df8[8];
-                            for (int f = 0; f < 8; ++f) Df8[f] = f < C::NTR ? lds[C::F_RING + C::P_FD + f] : 0.0;
+                            for (int f = 0; f < 8; ++f) Df8[f] = f < C::L.NTR ? lds[C::L.F_RING + C::L.P_FD + f] : 0.0;
                             printf("STF agent %lld stage %d facets D %.3e %.3e %.3e %.3e %.3e %.3e %.3e %.3e\n", agent, ts,
                                    Df8[0], Df8[1], Df8[2], Df8[3], Df8[4], Df8[5], Df8[6], Df8[7]);
                         }
@@ -1348,12 +864,12 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 {  // every lane runs the solve (lanes >= 2 NX on a copy of column 0, results to the sinks)
                     const bool kl = sl < 2 * NX;
                     const int c = kl ? sl : 0;
-                    const int off = c < NX ? C::F_SH + c * NU : C::F_W2 + (c - NX) * NU;
+                    const int off = c < NX ? C::L.F_SH + c * NU : C::L.F_W2 + (c - NX) * NU;
                     double x[NU];
 #pragma unroll
                     for (int i = 0; i < NU; ++i) x[i] = lds[off + i];
                     ldl_solve(x);
-                    if constexpr (C::STF) {
+                    if constexpr (C::L.STF) {
                         // x -= W C^-1 G'x; the multiplier-step coefficients -C^-1 G'x -> Gamma / Gamma_kappa
                         double gx[PMA], zc[PMA];
 #pragma unroll
@@ -1379,16 +895,16 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
                             for (int i = 0; i < PM; ++i) x[j] = fma(-Wm[j * PM + i], zc[i], x[j]);
                         }
-                        const int gb = c < NX ? C::B_GAM + c : C::B_GAK + c - NX;
+                        const int gb = c < NX ? C::L.B_GAM + c : C::L.B_GAK + c - NX;
 #pragma unroll
-                        for (int i = 0; i < PM; ++i) wb.st((kl ? gb + i * NX : C::B_JNK) * 8, fbo, fx ? 0.0 : -zc[i]);
+                        for (int i = 0; i < PM; ++i) wb.st((kl ? gb + i * NX : C::L.B_JNK) * 8, fbo, fx ? 0.0 : -zc[i]);
                     }
-                    const int g = c < NX ? C::B_K + c : C::B_KAP + c - NX;
+                    const int g = c < NX ? C::L.B_K + c : C::L.B_KAP + c - NX;
 #pragma unroll
                     for (int i = 0; i < NU; ++i) {
                         const double v = fx ? 0.0 : -x[i];
-                        lds[kl ? C::F_KK + c * NU + i : C::F_SINK] = v;
-                        wb.st((kl ? g + i * NX : C::B_JNK) * 8, fbo, v);
+                        lds[kl ? C::L.F_KK + c * NU + i : C::L.F_SINK] = v;
+                        wb.st((kl ? g + i * NX : C::L.B_JNK) * 8, fbo, v);
                     }
                 }
                 {   // lane e < NU^2 stores element e of [L | 1/d] (zero above the diagonal)
@@ -1398,9 +914,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                         const int ei = e / NU, ej = e % NU;
                         if (ei >= ej) v = (sl == e) ? (ei > ej ? Lm[e] : dinv[ei]) : v;
                     }
-                    wb.st((sl < NU * NU ? C::B_LD + sl : C::B_JNK) * 8, fbo, v);
+                    wb.st((sl < NU * NU ? C::L.B_LD + sl : C::L.B_JNK) * 8, fbo, v);
                 }
-                if constexpr (C::STF) {   // lane e < NSMB stores element e of W | C^-1 | stiff indices
+                if constexpr (C::L.STF) {   // lane e < NSMB stores element e of W | C^-1 | stiff indices
                     double v = 0.0;
 #pragma unroll
                     for (int e = 0; e < NU * PM; ++e) v = (sl == e) ? Wm[e] : v;
@@ -1408,10 +924,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     for (int e = 0; e < PM * PM; ++e) v = (sl == NU * PM + e) ? Ci[e] : v;
 #pragma unroll
                     for (int e = 0; e < PM; ++e) v = (sl == NU * PM + PM * PM + e) ? (double)sfi[e] : v;
-                    wb.st((sl < C::NSMB ? C::B_WS + sl : C::B_JNK) * 8, fbo, v);
+                    wb.st((sl < C::L.NSMB ? C::L.B_WS + sl : C::L.B_JNK) * 8, fbo, v);
                 }
                 };
-                if constexpr (C::STF) {
+                if constexpr (C::L.STF) {
                     if (__builtin_amdgcn_readfirstlane((int)(dfmr > 0.0))) ph3(std::true_type{});
                     else ph3(std::false_type{});
                 } else {
@@ -1426,13 +942,13 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             if (ts > 0) pf_store(ts - 1, cb);
             wsync();
             pstamp(14);
-            if constexpr (C::NV > 0) {
+            if constexpr (C::L.NV > 0) {
                 // ---- phase 5 (virtual control): the chain matrix Acl~ = G^-1 D Acl -> global (row-major)
 #pragma unroll
                 for (int r = 0; r < R0; ++r) {
                     const int o = sl + r * WAVE, oo = o < NX * NX ? o : 0, i = oo / NX, j = oo - i * NX;
-                    const double v = qp_dot<NX>(lds, C::F_Z + i * NX, C::F_ACLC + j * NX);
-                    wb.st((o < NX * NX ? C::B_ACL2 + o : C::B_JNK) * 8, fbo, v);
+                    const double v = qp_dot<NX>(lds, C::L.F_Z + i * NX, C::L.F_ACLC + j * NX);
+                    wb.st((o < NX * NX ? C::L.B_ACL2 + o : C::L.B_JNK) * 8, fbo, v);
                 }
                 wsync();
             }
@@ -1487,7 +1003,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 if (d4[r][2] >= 0 && ((d4[r][2] >> 15) & 1)) lds[d4[r][2] & 0x7FFF] = a4[r];
         }
         wsync();
-        if constexpr (C::NV > 0) {
+        if constexpr (C::L.NV > 0) {
 #pragma unroll
             for (int r = 0; r < R0; ++r) {
                 const int o = lane + r * WAVE;
@@ -1496,7 +1012,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             wsync();
         }
         // Pi_0 -> persistent; LU with partial pivoting of M (lane 0, registers)
-        for (int e = lane; e < NX * NX; e += WAVE) lds[V_PI0 + e] = lds[C::F_PIP + (e % NX) * NX + e / NX];
+        for (int e = lane; e < NX * NX; e += WAVE) lds[V_PI0 + e] = lds[C::L.F_PIP + (e % NX) * NX + e / NX];
         if constexpr (NX > 8) {
             // n = 12 classes: the same LU column-parallel (lane j < NX owns column j of M; pivot column k
             // broadcast by readlane) -- the lane-0 form holds NX x NX doubles in registers and spills.  Every
@@ -1582,7 +1098,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         }
         }
         wsync();
-        if constexpr (C::CHK) {
+        if constexpr (C::L.CHK) {
             const ChunkC cc = chunk_coords();
             const int ch = cc.ch, ce = cc.ce, cs0 = cc.cs0, cs1 = cc.cs1;
             const bool cact = cc.act;
@@ -1593,7 +1109,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
             for (int j = 0; j < QP_CLM; ++j) {
                 const int tj = cs0 + j;
-                const int vo = (cact && j < CL && tj < cs1) ? (C::B_CH + ce * NX) * 8 + tj * C::FBS * 8 : QP_OOB;
+                const int vo = (cact && j < CL && tj < cs1) ? (C::L.B_CH + ce * NX) * 8 + tj * C::L.FBS * 8 : QP_OOB;
 #pragma unroll
                 for (int k = 0; k < NX; ++k) {
                     if constexpr (NX % 2 == 0) { if (!(k & 1)) wld2(&ar[j][k], vo, FBB, k * 8); }   // rows start even
@@ -1618,7 +1134,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 }
             }
 #pragma unroll
-            for (int c = 0; c < NX; ++c) lds[cact ? V_PHI + ch * NX * NX + ce * NX + c : C::F_SINK] = ph[c];
+            for (int c = 0; c < NX; ++c) lds[cact ? V_PHI + ch * NX * NX + ce * NX + c : C::L.F_SINK] = ph[c];
             wsync();
         }
         return lds[V_FLAG] == 0.0;
@@ -1632,10 +1148,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     // Virtual control: stage t sees P~ = D G^-1 P_{t+1} and p~ = p_{t+1} - (G^-1 P)'(p_{t+1} + d) in place of
     // P_{t+1}, p_{t+1} (oracle/scvx_cpu.cpp riccati_factor), the chains run on Acl~ = G^-1 D Acl, and
     // nu_t = xi_{t+1} - (A xi_t + Bt du_t + e_t) comes out of the forward chain.
-    // rhs_s: rho of the stage's stiff facets (C::STF; 0 in empty slots), fnu: their multiplier steps (out)
+    // rhs_s: rho of the stage's stiff facets (C::L.STF; 0 in empty slots), fnu: their multiplier steps (out)
     auto solve = [&](const double* q, const double* r, const double* dv, double* dzo, double* dyo, double* dno,
                      const double* rhs_s, double* fnu) __attribute__((always_inline)) {
-        constexpr int PM = C::PM, PMA = C::PMA;
+        constexpr int PM = C::L.PM, PMA = C::L.PMA;
         double g0[PMA];   // nu's feed-forward part gamma0 = -C^-1 (G' R0^-1 rh + rho) (stiff facets)
 #pragma unroll
         for (int i = 0; i < PMA; ++i) { g0[i] = 0.0; fnu[i] = 0.0; }
@@ -1643,10 +1159,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         fresh();
         if (act) {
             double g[NX], u[NX];
-            ldb(u, C::B_U, NX);
+            ldb(u, C::L.B_U, NX);
             if constexpr (NV > 0) {
                 double Y[NX * NX];
-                ldb(Y, C::B_YP, NX * NX);
+                ldb(Y, C::L.B_YP, NX * NX);
                 hold(u, NX);
                 hold(Y, NX * NX);
 #pragma unroll
@@ -1655,17 +1171,17 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     for (int i = 0; i < NX; ++i) u[j] = fma(-Y[j * NX + i], dv[i], u[j]);
             }
             double Kt[NU * NX], Ac[NX * NX];
-            ldb(Kt, C::B_K, NU * NX);
-            ldb(Ac, C::B_ACL, NX * NX);
+            ldb(Kt, C::L.B_K, NU * NX);
+            ldb(Ac, C::L.B_ACL, NX * NX);
             hold(Kt, NU * NX);
             hold(u, NX);
             hold(Ac, NX * NX);
 #pragma unroll
             for (int i = 0; i < NX; ++i) g[i] = q[i];
-            if constexpr (C::STF) {
+            if constexpr (C::L.STF) {
                 if (stf_any()) {
                     double Gm[PMA * NX];
-                    ldb(Gm, C::B_GAM, PM * NX);
+                    ldb(Gm, C::L.B_GAM, PM * NX);
                     hold(Gm, PM * NX);
 #pragma unroll
                     for (int i = 0; i < PM; ++i)
@@ -1688,9 +1204,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         }
         wsync();
         stamp(4);
-        if constexpr (C::CHK) {
+        if constexpr (C::L.CHK) {
             const ChunkC cc = chunk_coords();
-            const int ch = cc.ch, ce = cc.ce, cs0 = cc.cs0, cs1 = cc.cs1;
+            const int ce = cc.ce, cs0 = cc.cs0, cs1 = cc.cs1;
             const bool cact = cc.act;
             // chunked: p_{s0} = Phi_c' p_{s1} + q_c per chunk (q_c the chunk's chain from p_{s1} = 0), so
             //   A  every chunk runs its own CL steps from 0 (the last chunk from p_{K-1} = g_{K-1}: exact),
@@ -1704,7 +1220,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             for (int j = 0; j < QP_CLM; ++j) {
                 const int tj = cs1 - 1 - j;
                 const bool ok = cact && j < CL && tj >= cs0;
-                const int vo = ok ? (C::B_CH + ce) * 8 + tj * C::FBS * 8 : QP_OOB;
+                const int vo = ok ? (C::L.B_CH + ce) * 8 + tj * C::L.FBS * 8 : QP_OOB;
 #pragma unroll
                 for (int k = 0; k < NX; ++k) ac[j][k] = wld(vo, FBB, k * NX * 8);
                 gc[j] = lds[V_G + (ok ? tj : 0) * NX + (ce < NX ? ce : 0)];
@@ -1728,7 +1244,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     q = (cs1 - 1 - j >= cs0) ? qn : q;
                 }
             }
-            lds[cact ? V_CH + cs0 * NX + ce : C::F_SINK] = q;
+            lds[cact ? V_CH + cs0 * NX + ce : C::L.F_SINK] = q;
             wsync();
             if (lane < NX) {
                 double p = lds[V_CH + min((NCH - 1) * CL, KS) * NX + lane];
@@ -1752,7 +1268,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     const int tj = cs1 - 1 - j;
                     const double pn = chainT(p, ac[j], gc[j]);
                     p = tj >= cs0 ? pn : p;
-                    lds[(cact && tj > cs0) ? V_CH + tj * NX + ce : C::F_SINK] = p;
+                    lds[(cact && tj > cs0) ? V_CH + tj * NX + ce : C::L.F_SINK] = p;
                 }
             }
         } else {
@@ -1760,11 +1276,11 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             // from lanes 0..NX-1 by a DPP row broadcast (NX <= 16), the Acl column / g of the next stage read ahead
             if (lane < NX) {
                 // lane i needs column i of Acl_t (stage block, B_CH + k*NX + i; Acl~ for VC)
-                const int va = (C::B_CH + lane) * 8;
+                const int va = (C::L.B_CH + lane) * 8;
                 auto ldA = [&](int ts, double* an, double& gn) __attribute__((always_inline)) {
                     const int tc = ts > 0 ? ts : 0;
     #pragma unroll
-                    for (int k = 0; k < NX; ++k) an[k] = wb.ld(va + k * NX * 8, FBB + tc * C::FBS * 8);
+                    for (int k = 0; k < NX; ++k) an[k] = wb.ld(va + k * NX * 8, FBB + tc * C::L.FBS * 8);
                     gn = lds[V_G + tc * NX + lane];
                 };
                 auto chain = [&](double p, const double* ac, double g) __attribute__((always_inline)) -> double {
@@ -1813,10 +1329,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         for (int j = 0; j < NU; ++j) k0[j] = 0.0;
         if (act) {
             double uu[NX], Bt[NX * NU], Ld[NU * NU], W2[NU * NX];
-            ldb(uu, C::B_U, NX);
-            ldn(Bt, C::C_BT, NX * NU);
-            ldb(Ld, C::B_LD, NU * NU);
-            ldb(W2, C::B_W2, NU * NX);
+            ldb(uu, C::L.B_U, NX);
+            ldn(Bt, C::L.C_BT, NX * NU);
+            ldb(Ld, C::L.B_LD, NU * NU);
+            ldb(W2, C::L.B_W2, NU * NX);
             hold(uu, NX); hold(Bt, NX * NU); hold(Ld, NU * NU); hold(W2, NU * NX);
 #pragma unroll
             for (int i = 0; i < NX; ++i) pv[i] = lds[V_CH + t * NX + i];
@@ -1832,13 +1348,13 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     double Y[NX * NX], w[NX];
 #pragma unroll
                     for (int i = 0; i < NX; ++i) w[i] = pn[i] + dv[i];
-                    ldb(Y, C::B_YP, NX * NX);
+                    ldb(Y, C::L.B_YP, NX * NX);
                     hold(Y, NX * NX);
 #pragma unroll
                     for (int j = 0; j < NX; ++j)
 #pragma unroll
                         for (int i = 0; i < NX; ++i) pn[j] = fma(-Y[j * NX + i], w[i], pn[j]);
-                    ldb(Y, C::B_YPI, NX * NX);
+                    ldb(Y, C::L.B_YPI, NX * NX);
                     hold(Y, NX * NX);
 #pragma unroll
                     for (int j = 0; j < NX; ++j)
@@ -1868,11 +1384,11 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 for (int k = i + 1; k < NU; ++k) v -= Ld[k * NU + i] * k0[k];
                 k0[i] = v;
             }
-            if constexpr (C::STF) if (stf_any()) {
+            if constexpr (C::L.STF) if (stf_any()) {
                 // a = R0^-1 rh (k0 here); gamma0 = -C^-1 (G'a + rho); k0 = -(a + W gamma0)
-                double sm[C::NSMB];
-                ldb(sm, C::B_WS, C::NSMB);
-                hold(sm, C::NSMB);
+                double sm[C::L.NSMB];
+                ldb(sm, C::L.B_WS, C::L.NSMB);
+                hold(sm, C::L.NSMB);
                 const double* Wm = sm;
                 const double* Ci = sm + NU * PM;
                 const double* sf = sm + NU * PM + PM * PM;
@@ -1946,11 +1462,11 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         for (int j = 0; j < NU; ++j) v0[j] = k0[j];
         if (act) {
             double kap[NU * NX], Pi[NX * NX], Bt[NX * NU], ev[NX];
-            ldb(kap, C::B_KAP, NU * NX);
-            ldb(Pi, C::B_PI, NX * NX);
-            ldn(Bt, C::C_BT, NX * NU);
+            ldb(kap, C::L.B_KAP, NU * NX);
+            ldb(Pi, C::L.B_PI, NX * NX);
+            ldn(Bt, C::L.C_BT, NX * NU);
 #pragma unroll
-            for (int i = 0; i < NX; ++i) ev[i] = pld(C::gE + i);
+            for (int i = 0; i < NX; ++i) ev[i] = pld(C::L.gE + i);
             hold(kap, NU * NX); hold(Pi, NX * NX); hold(Bt, NX * NU); hold(ev, NX);
 #pragma unroll
             for (int i = 0; i < NU; ++i)
@@ -1973,8 +1489,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     // f~ = G^-1 (D o f - p_{t+1} - d) - (G^-1 Pi) mu   (V_CH still holds the backward chain)
                     double Y[NX * NX], w[NX];
 #pragma unroll
-                    for (int i = 0; i < NX; ++i) w[i] = fma(pld(C::gD + i), fv[i], -lds[V_CH + (t + 1) * NX + i] - dv[i]);
-                    ldb(Y, C::B_GI, NX * NX);
+                    for (int i = 0; i < NX; ++i) w[i] = fma(pld(C::L.gD + i), fv[i], -lds[V_CH + (t + 1) * NX + i] - dv[i]);
+                    ldb(Y, C::L.B_GI, NX * NX);
                     hold(Y, NX * NX);
 #pragma unroll
                     for (int i = 0; i < NX; ++i) {
@@ -1983,7 +1499,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                         for (int j = 0; j < NX; ++j) v = fma(Y[j * NX + i], w[j], v);
                         fv[i] = v;
                     }
-                    ldb(Y, C::B_YPI, NX * NX);
+                    ldb(Y, C::L.B_YPI, NX * NX);
                     hold(Y, NX * NX);
 #pragma unroll
                     for (int i = 0; i < NX; ++i)
@@ -1996,7 +1512,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         }
         wsync();
         stamp(7);
-        if constexpr (C::CHK) {
+        if constexpr (C::L.CHK) {
             const ChunkC cc = chunk_coords();
             const int ch = cc.ch, ce = cc.ce, cs0 = cc.cs0, cs1 = cc.cs1;
             const bool cact = cc.act;
@@ -2010,7 +1526,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             for (int j = 0; j < QP_CLM; ++j) {
                 const int tj = cs0 + j;
                 const bool ok = cact && j < CL && tj < cs1;
-                const int vo = ok ? (C::B_CH + ce * NX) * 8 + tj * C::FBS * 8 : QP_OOB;
+                const int vo = ok ? (C::L.B_CH + ce * NX) * 8 + tj * C::L.FBS * 8 : QP_OOB;
 #pragma unroll
                 for (int k = 0; k < NX; ++k) {
                     if constexpr (NX % 2 == 0) { if (!(k & 1)) wld2(&ar[j][k], vo, FBB, k * 8); }   // rows start even
@@ -2036,7 +1552,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     x = (cs0 + j < cs1) ? xn : x;
                 }
             }
-            lds[cact ? V_CH + cs1 * NX + ce : C::F_SINK] = x;
+            lds[cact ? V_CH + cs1 * NX + ce : C::L.F_SINK] = x;
             if (lane < NX) lds[V_CH + lane] = x0;
             wsync();
             if (lane < NX) {
@@ -2063,18 +1579,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     const double xn = chainF(x, ar[j], fr[j]);
                     const bool ok = tj < cs1;
                     x = ok ? xn : x;
-                    lds[(cact && ok && (tj + 1 < cs1 || tj + 1 == KS)) ? V_CH + (tj + 1) * NX + ce : C::F_SINK] = x;
+                    lds[(cact && ok && (tj + 1 < cs1 || tj + 1 == KS)) ? V_CH + (tj + 1) * NX + ce : C::L.F_SINK] = x;
                 }
             }
         } else {
             // ---- forward chain xi_{t+1} = Acl_t xi_t + f_t
             if (lane < NX) {
                 // lane i needs row i of Acl_t (stage block, B_CH + i*NX + k; Acl~ for VC)
-                const int va = (C::B_CH + lane * NX) * 8;
+                const int va = (C::L.B_CH + lane * NX) * 8;
                 auto ldA = [&](int ts, double* an, double& fn) __attribute__((always_inline)) {
                     const int tc = ts < K - 1 ? ts : K - 2;
     #pragma unroll
-                    for (int k = 0; k < NX; ++k) an[k] = wb.ld(va + k * 8, FBB + tc * C::FBS * 8);
+                    for (int k = 0; k < NX; ++k) an[k] = wb.ld(va + k * 8, FBB + tc * C::L.FBS * 8);
                     fn = lds[V_G + tc * NX + lane];
                 };
                 auto chain = [&](double x, const double* ac, double f) __attribute__((always_inline)) -> double {
@@ -2120,8 +1636,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         for (int i = 0; i < NV; ++i) dno[i] = 0.0;
         if (act) {
             double xi[NX], Cp[NX * NU], Kt[NU * NX], P[NX * NX];
-            ldb(Kt, C::B_K, NU * NX);
-            ldb(P, C::B_P, NX * NX);
+            ldb(Kt, C::L.B_K, NU * NX);
+            ldb(P, C::L.B_P, NX * NX);
             load_cp(Cp);
             hold(Kt, NU * NX); hold(P, NX * NX);
 #pragma unroll
@@ -2147,12 +1663,12 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             }
 #pragma unroll
             for (int j = 0; j < NU; ++j) dzo[NX + j] = du[j];
-            if constexpr (C::STF) if (stf_any()) {
+            if constexpr (C::L.STF) if (stf_any()) {
                 // the stiff facets' multiplier steps nu = Gamma xi + Gamma_kappa mu + gamma0 (no D (g'du - rho): the
                 // product of a ~1e12 weight and a cancelling difference)
                 double Gm[PMA * NX], Gk[PMA * NX];
-                ldb(Gm, C::B_GAM, PM * NX);
-                ldb(Gk, C::B_GAK, PM * NX);
+                ldb(Gm, C::L.B_GAM, PM * NX);
+                ldb(Gk, C::L.B_GAK, PM * NX);
                 hold(Gm, PM * NX); hold(Gk, PM * NX);
 #pragma unroll
                 for (int i = 0; i < PM; ++i) {
@@ -2165,10 +1681,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             if constexpr (NV > 0) {
                 // dnu_t = xi_{t+1} - (A xi_t + Bt du_t + e_t)
                 double Ad[NX * NX], Bt[NX * NU], ev[NX];
-                ldn(Ad, C::C_DT, NX * NX);
-                ldn(Bt, C::C_BT, NX * NU);
+                ldn(Ad, C::L.C_DT, NX * NX);
+                ldn(Bt, C::L.C_BT, NX * NU);
 #pragma unroll
-                for (int i = 0; i < NX; ++i) ev[i] = pld(C::gE + i);
+                for (int i = 0; i < NX; ++i) ev[i] = pld(C::L.gE + i);
                 hold(Ad, NX * NX); hold(Bt, NX * NU); hold(ev, NX);
 #pragma unroll
                 for (int i = 0; i < NX; ++i) {
@@ -2201,54 +1717,54 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     constexpr int NSR = SGS ? 1 : NSA;
     double z[NZ], y[NX], sq[NQ], lq[NQ], av[NGA], ub[NU], sg[NSR][3], sb[NSR];
     auto sgv = [&](int q, int i) __attribute__((always_inline)) -> double {
-        if constexpr (SGS) return wld(qp_opaque(vt), (C::C_SOFT + q * 4 + i) * colb);
+        if constexpr (SGS) return wld(qp_opaque(vt), (C::L.C_SOFT + q * 4 + i) * colb);
         else return i < 3 ? sg[q][i] : sb[q];
     };
     // virtual control state of this node (VC classes, lanes t < K-1): nu, e, and per component the slacks /
     // duals of the rows nu - e <= 0 (index 2i) and -nu - e <= 0 (2i + 1)
     double vn[NVA], ve[NVA], vs[2 * NVA], vl[2 * NVA];
     // row slacks s_r and duals lambda_r of this node: LDS [r][lane]
-    // (n = 12 classes: workspace columns C_RS / C_RL, C::ROWG)
+    // (n = 12 classes: workspace columns C_RS / C_RL, C::L.ROWG)
     auto s_ = [&](int r) __attribute__((always_inline)) -> double {
-        if constexpr (C::ROWG) return cld(C::C_RS + r);
+        if constexpr (C::L.ROWG) return cld(C::L.C_RS + r);
         else return lds[V_S + r * WAVE + lane];
     };
     auto l_ = [&](int r) __attribute__((always_inline)) -> double {
-        if constexpr (C::ROWG) return cld(C::C_RL + r);
+        if constexpr (C::L.ROWG) return cld(C::L.C_RL + r);
         else return lds[V_L + r * WAVE + lane];
     };
     auto s_set = [&](int r, double v) __attribute__((always_inline)) {
-        if constexpr (C::ROWG) cst(C::C_RS + r, v);
+        if constexpr (C::L.ROWG) cst(C::L.C_RS + r, v);
         else lds[V_S + r * WAVE + lane] = v;
     };
     auto l_set = [&](int r, double v) __attribute__((always_inline)) {
-        if constexpr (C::ROWG) cst(C::C_RL + r, v);
+        if constexpr (C::L.ROWG) cst(C::L.C_RL + r, v);
         else lds[V_L + r * WAVE + lane] = v;
     };
     int bidx[NBA];
     auto issue_state = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < NZ; ++i) z[i] = cld(C::C_Z + i);
+        for (int i = 0; i < NZ; ++i) z[i] = cld(C::L.C_Z + i);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) y[i] = cld(C::C_Y + i);
+        for (int i = 0; i < NX; ++i) y[i] = cld(C::L.C_Y + i);
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) { sq[j] = cld(C::C_SQ + j); lq[j] = cld(C::C_LQ + j); }
+        for (int j = 0; j < NQ; ++j) { sq[j] = cld(C::L.C_SQ + j); lq[j] = cld(C::L.C_LQ + j); }
 #pragma unroll
-        for (int g = 0; g < NGA; ++g) av[g] = g < NG ? cld(C::C_AV + g) : 0.0;
+        for (int g = 0; g < NGA; ++g) av[g] = g < NG ? cld(C::L.C_AV + g) : 0.0;
 #pragma unroll
-        for (int j = 0; j < NU; ++j) ub[j] = cld(C::C_UB + j);
+        for (int j = 0; j < NU; ++j) ub[j] = cld(C::L.C_UB + j);
 #pragma unroll
         for (int q = 0; q < (SGS ? 0 : NS); ++q) {
 #pragma unroll
-            for (int i = 0; i < 3; ++i) sg[q][i] = cld(C::C_SOFT + q * 4 + i);
-            sb[q] = cld(C::C_SOFT + q * 4 + 3);
+            for (int i = 0; i < 3; ++i) sg[q][i] = cld(C::L.C_SOFT + q * 4 + i);
+            sb[q] = cld(C::L.C_SOFT + q * 4 + 3);
         }
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            vn[i] = cld(C::C_VN + i);
-            ve[i] = cld(C::C_VE + i);
-            vs[2 * i] = cld(C::C_VS + 2 * i); vs[2 * i + 1] = cld(C::C_VS + 2 * i + 1);
-            vl[2 * i] = cld(C::C_VL + 2 * i); vl[2 * i + 1] = cld(C::C_VL + 2 * i + 1);
+            vn[i] = cld(C::L.C_VN + i);
+            ve[i] = cld(C::L.C_VE + i);
+            vs[2 * i] = cld(C::L.C_VS + 2 * i); vs[2 * i + 1] = cld(C::L.C_VS + 2 * i + 1);
+            vl[2 * i] = cld(C::L.C_VL + 2 * i); vl[2 * i + 1] = cld(C::L.C_VL + 2 * i + 1);
         }
     };
     auto hold_state = [&]() __attribute__((always_inline)) {
@@ -2266,28 +1782,28 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     };
     auto store_state = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < NZ; ++i) cst(C::C_Z + i, z[i]);
+        for (int i = 0; i < NZ; ++i) cst(C::L.C_Z + i, z[i]);
 #pragma unroll
-        for (int i = 0; i < NX; ++i) cst(C::C_Y + i, y[i]);
+        for (int i = 0; i < NX; ++i) cst(C::L.C_Y + i, y[i]);
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) { cst(C::C_SQ + j, sq[j]); cst(C::C_LQ + j, lq[j]); }
+        for (int j = 0; j < NQ; ++j) { cst(C::L.C_SQ + j, sq[j]); cst(C::L.C_LQ + j, lq[j]); }
 #pragma unroll
-        for (int g = 0; g < NG; ++g) cst(C::C_AV + g, av[g]);
+        for (int g = 0; g < NG; ++g) cst(C::L.C_AV + g, av[g]);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            cst(C::C_VN + i, vn[i]);
-            cst(C::C_VE + i, ve[i]);
-            cst(C::C_VS + 2 * i, vs[2 * i]); cst(C::C_VS + 2 * i + 1, vs[2 * i + 1]);
-            cst(C::C_VL + 2 * i, vl[2 * i]); cst(C::C_VL + 2 * i + 1, vl[2 * i + 1]);
+            cst(C::L.C_VN + i, vn[i]);
+            cst(C::L.C_VE + i, ve[i]);
+            cst(C::L.C_VS + 2 * i, vs[2 * i]); cst(C::L.C_VS + 2 * i + 1, vs[2 * i + 1]);
+            cst(C::L.C_VL + 2 * i, vl[2 * i]); cst(C::L.C_VL + 2 * i + 1, vl[2 * i + 1]);
         }
     };
     auto grp_on = [&](int g) __attribute__((always_inline)) -> bool { return ineq && (g < NO ? g < nobs : has_coll); };
     auto row_on = [&](int r) __attribute__((always_inline)) -> bool {
-        if (r < C::R_BOX) return ineq;
-        if (r < C::R_OBS) return ineq && ((r - C::R_BOX) >> 1) < nbox;
-        if (r < C::R_COL) return ineq && (r - C::R_OBS) < nobs;
-        if (r < C::R_GRP) return (r - C::R_COL) < ccount;
-        return grp_on(r - C::R_GRP);
+        if (r < C::L.R_BOX) return ineq;
+        if (r < C::L.R_OBS) return ineq && ((r - C::L.R_BOX) >> 1) < nbox;
+        if (r < C::L.R_COL) return ineq && (r - C::L.R_OBS) < nobs;
+        if (r < C::L.R_GRP) return (r - C::L.R_COL) < ccount;
+        return grp_on(r - C::L.R_GRP);
     };
     auto sel_x = [&](const double* zz, int idx) __attribute__((always_inline)) -> double {
         double v = 0.0;
@@ -2297,7 +1813,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     };
     // G_r [z; a] and h_r of row r (static after unrolling)
     auto row_eval = [&](int r, const double* zz, const double* aa, double& gz, double& h) __attribute__((always_inline)) {
-        if (r < C::R_BOX) {
+        if (r < C::L.R_BOX) {
             gz = 0.0; h = trv;
 #pragma unroll
             for (int j = 0; j < NU; ++j) {
@@ -2305,43 +1821,43 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 gz += neg ? -zz[NX + j] : zz[NX + j];
                 h += neg ? -ub[j] : ub[j];
             }
-        } else if (r < C::R_OBS) {
-            const int b = (r - C::R_BOX) >> 1, lo = (r - C::R_BOX) & 1;
+        } else if (r < C::L.R_OBS) {
+            const int b = (r - C::L.R_BOX) >> 1, lo = (r - C::L.R_BOX) & 1;
             const double xi = sel_x(zz, bidx[b]);
             gz = lo ? -xi : xi; h = lo ? -T.box_lo[b] : T.box_hi[b];
-        } else if (r < C::R_GRP) {
-            const int q = r - C::R_OBS, g = q < NO ? q : NO;
+        } else if (r < C::L.R_GRP) {
+            const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
             gz = -(sgv(q, 0) * zz[0] + sgv(q, 1) * zz[1] + sgv(q, 2) * zz[2]) - aa[g];
             h = -sgv(q, 3);
         } else {
-            gz = -aa[r - C::R_GRP]; h = 0.0;
+            gz = -aa[r - C::L.R_GRP]; h = 0.0;
         }
     };
     // gzv += c G_r'|_z, gav += c G_r'|_a
     auto row_accT = [&](int r, double c, double* gzv, double* gav) __attribute__((always_inline)) {
-        if (r < C::R_BOX) {
+        if (r < C::L.R_BOX) {
 #pragma unroll
             for (int j = 0; j < NU; ++j) gzv[NX + j] += ((r >> j) & 1) ? -c : c;
-        } else if (r < C::R_OBS) {
-            const int b = (r - C::R_BOX) >> 1, lo = (r - C::R_BOX) & 1, idx = bidx[b];
+        } else if (r < C::L.R_OBS) {
+            const int b = (r - C::L.R_BOX) >> 1, lo = (r - C::L.R_BOX) & 1, idx = bidx[b];
 #pragma unroll
             for (int i = 0; i < NX; ++i) gzv[i] = fma(qp_mask(i, idx), lo ? -c : c, gzv[i]);
-        } else if (r < C::R_GRP) {
-            const int q = r - C::R_OBS, g = q < NO ? q : NO;
+        } else if (r < C::L.R_GRP) {
+            const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
 #pragma unroll
             for (int i = 0; i < 3; ++i) gzv[i] -= c * sgv(q, i);
             gav[g] -= c;
         } else {
-            gav[r - C::R_GRP] -= c;
+            gav[r - C::L.R_GRP] -= c;
         }
     };
     // gav += c G_r'|_a (group part only)
     auto row_accA = [&](int r, double c, double* gav) __attribute__((always_inline)) {
-        if (r >= C::R_OBS && r < C::R_GRP) {
-            const int q = r - C::R_OBS;
+        if (r >= C::L.R_OBS && r < C::L.R_GRP) {
+            const int q = r - C::L.R_OBS;
             gav[q < NO ? q : NO] -= c;
-        } else if (r >= C::R_GRP) {
-            gav[r - C::R_GRP] -= c;
+        } else if (r >= C::L.R_GRP) {
+            gav[r - C::L.R_GRP] -= c;
         }
     };
     auto gweight = [&](int g) __attribute__((always_inline)) -> double { return (g < NO ? T.w_obs : T.w_coll) * iosc; };
@@ -2349,7 +1865,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     // Node Hessian (row scaling D_r = l/s or 1, SOC block Wi2uu) -> packet Q, S, R (xi/u
     // coordinates); group elimination factors -> columns C_GRP.  Also writes e = -rp.
     auto assemble = [&](bool unit, const double* Wi2uu, const double* rp) __attribute__((always_inline)) {
-        double dbox[NX], Hpp[3][3], Huu[NU * NU], Dfc[C::STF ? C::NTR : 1];
+        double dbox[NX], Hpp[3][3], Huu[NU * NU], Dfc[C::L.STF ? C::L.NTR : 1];
 #pragma unroll
         for (int i = 0; i < NX; ++i) dbox[i] = 2.0 * (wfs + wpx);
 #pragma unroll
@@ -2364,8 +1880,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             const double Dr = row_on(r) ? (unit ? 1.0 : qp_div(l_(r), s_(r))) : 0.0;
-            if (r < C::R_BOX) {
-                if constexpr (C::STF) {
+            if (r < C::L.R_BOX) {
+                if constexpr (C::L.STF) {
                     Dfc[r] = Dr;   // folded below, all but the stiff ones
                 } else {
 #pragma unroll
@@ -2373,18 +1889,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
                         for (int j = 0; j < NU; ++j) Huu[i * NU + j] += (((r >> i) ^ (r >> j)) & 1) ? -Dr : Dr;
                 }
-            } else if (r < C::R_OBS) {
-                const int idx = bidx[(r - C::R_BOX) >> 1];
+            } else if (r < C::L.R_OBS) {
+                const int idx = bidx[(r - C::L.R_BOX) >> 1];
 #pragma unroll
                 for (int i = 0; i < NX; ++i) dbox[i] = fma(qp_mask(i, idx), Dr, dbox[i]);
-            } else if (r < C::R_GRP) {
-                const int q = r - C::R_OBS, g = q < NO ? q : NO;
+            } else if (r < C::L.R_GRP) {
+                const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
                 Haa[g] += Dr;
 #pragma unroll
                 for (int i = 0; i < 3; ++i) Hpa[g][i] += Dr * sgv(q, i);
             } else {
-                Haa[r - C::R_GRP] += Dr;
-                D0[r - C::R_GRP] = Dr;
+                Haa[r - C::L.R_GRP] += Dr;
+                D0[r - C::L.R_GRP] = Dr;
             }
         }
         // slack groups eliminated: the position block gains H_pp - H_pa H_aa^-1 H_ap, written as the weighted
@@ -2400,8 +1916,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             for (int i = 0; i < 3; ++i) hp[g][i] = Hpa[g][i] * ih;
             if (g < NG) {
 #pragma unroll
-                for (int i = 0; i < 3; ++i) cst(C::C_GRP + g * 4 + i, hp[g][i]);
-                cst(C::C_GRP + g * 4 + 3, ih);
+                for (int i = 0; i < 3; ++i) cst(C::L.C_GRP + g * 4 + i, hp[g][i]);
+                cst(C::L.C_GRP + g * 4 + 3, ih);
             }
 #pragma unroll
             for (int i = 0; i < 3; ++i)
@@ -2409,9 +1925,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 for (int j = 0; j < 3; ++j) Hpp[i][j] = fma(D0[g] * hp[g][i], hp[g][j], Hpp[i][j]);
         }
 #pragma unroll
-        for (int r = C::R_OBS; r < C::R_GRP; ++r) {
+        for (int r = C::L.R_OBS; r < C::L.R_GRP; ++r) {
             const double Dr = row_on(r) ? (unit ? 1.0 : qp_div(l_(r), s_(r))) : 0.0;
-            const int q = r - C::R_OBS, g = q < NO ? q : NO;
+            const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
             double c[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) c[i] = sgv(q, i) - hp[g][i];
@@ -2426,7 +1942,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const double d1 = unit ? 1.0 : qp_div(vl[2 * i], vs[2 * i]), d2 = unit ? 1.0 : qp_div(vl[2 * i + 1], vs[2 * i + 1]);
-            pst(C::gD + i, vact ? qp_div(4.0 * d1 * d2, d1 + d2) : 1.0);
+            pst(C::L.gD + i, vact ? qp_div(4.0 * d1 * d2, d1 + d2) : 1.0);
         }
         double Q[NX * NX], Cp[NX * NU];
         load_cp(Cp);
@@ -2440,11 +1956,11 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 // global packet: the diagonal and the position block's off-diagonals (every other element is a
                 // structural zero: written at setup in the dense form, absent from the compact one, which
                 // keeps only the upper triangle)
-                if constexpr (C::DPK) {
-                    if (i == j || (i < 3 && j < 3)) pst(C::P_Q + i * NX + j, v);
+                if constexpr (C::L.DPK) {
+                    if (i == j || (i < 3 && j < 3)) pst(C::L.P_Q + i * NX + j, v);
                 } else {
-                    if (i == j) pst(C::G_QD + i, v);
-                    else if (i < j && j < 3) pst(C::G_QO + i + j - 1, v);
+                    if (i == j) pst(C::L.G_QD + i, v);
+                    else if (i < j && j < 3) pst(C::L.G_QO + i + j - 1, v);
                 }
             }
         double Sx[NX * NU];
@@ -2456,7 +1972,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
                 for (int k = 0; k < NX; ++k) v = fma(Q[i * NX + k], Cp[j * NX + k], v);
                 Sx[i * NU + j] = v;
-                pst(C::gS + i * NU + j, v);
+                pst(C::L.gS + i * NU + j, v);
             }
         double Ru[NU * NU];
 #pragma unroll
@@ -2468,18 +1984,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 for (int k = 0; k < NX; ++k) v = fma(Cp[i * NX + k], Sx[k * NU + j], v);
                 Ru[i * NU + j] = v;
             }
-        if constexpr (C::STF) {
+        if constexpr (C::L.STF) {
             // the facets' weights, their folded sum sum_f D_f g_f g_f' (the diagonal is sum_f D_f; off-diagonal (i, j) the
             // sum of D_f signed by the parity of facet bits i and j) and their max.  A facet can be stiff in its stage
             // (phase 3: above QP_STIFF x Rhat's largest diagonal) only if it is above QP_STIFF x R's (Rhat = R +
             // Bt'P Bt >= R): the other nodes (nearly all of them) fold their facets into R here and store dfm = 0, so
             // their stages run phase 3 without the facet branch
-            double dsum = 0.0, dfm = 0.0, osum[C::NFO > 0 ? C::NFO : 1];
+            double dsum = 0.0, dfm = 0.0, osum[C::L.NFO > 0 ? C::L.NFO : 1];
 #pragma unroll
-            for (int e = 0; e < C::NFO; ++e) osum[e] = 0.0;
+            for (int e = 0; e < C::L.NFO; ++e) osum[e] = 0.0;
 #pragma unroll
-            for (int f = 0; f < C::NTR; ++f) {
-                pst(C::gFD + f, Dfc[f]);
+            for (int f = 0; f < C::L.NTR; ++f) {
+                pst(C::L.gFD + f, Dfc[f]);
                 dsum += Dfc[f];
                 dfm = fmax(dfm, Dfc[f]);
                 int e = 0;
@@ -2501,36 +2017,36 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     for (int j = i + 1; j < NU; ++j, ++e) Ru[i * NU + j] += cand ? 0.0 : osum[e];
                 }
             }
-            pst(C::gFD + C::NTR, cand ? dsum : 0.0);
+            pst(C::L.gFD + C::L.NTR, cand ? dsum : 0.0);
 #pragma unroll
-            for (int e = 0; e < C::NFO; ++e) pst(C::gFD + C::NTR + 1 + e, cand ? osum[e] : 0.0);
-            pst(C::gFD + C::NTR + 1 + C::NFO, cand ? dfm : 0.0);
+            for (int e = 0; e < C::L.NFO; ++e) pst(C::L.gFD + C::L.NTR + 1 + e, cand ? osum[e] : 0.0);
+            pst(C::L.gFD + C::L.NTR + 1 + C::L.NFO, cand ? dfm : 0.0);
         }
 #pragma unroll
         for (int i = 0; i < NU; ++i)
 #pragma unroll
             for (int j = i; j < NU; ++j) {  // upper triangle: packed by rows (compact), both halves (dense)
                 const double v = Ru[i * NU + j];
-                if constexpr (C::DPK) {
-                    pst(C::P_R + i * NU + j, v);
-                    if (j > i) pst(C::P_R + j * NU + i, v);
+                if constexpr (C::L.DPK) {
+                    pst(C::L.P_R + i * NU + j, v);
+                    if (j > i) pst(C::L.P_R + j * NU + i, v);
                 } else {
-                    pst(C::G_R + i * NU - i * (i - 1) / 2 + (j - i), v);
+                    pst(C::L.G_R + i * NU - i * (i - 1) / 2 + (j - i), v);
                 }
             }
 #pragma unroll
-        for (int i = 0; i < NX; ++i) pst(C::gE + i, (t < K - 1) ? -rp[i] : 0.0);
+        for (int i = 0; i < NX; ++i) pst(C::L.gE + i, (t < K - 1) ? -rp[i] : 0.0);
     };
     // eliminate the group part of a Newton rhs (stores it for recover_aux): r1_p -= Hpa/Haa r1a;
     // returns the (xi, u) linear terms q, r of the node
     auto reduce_rhs = [&](double* r1, const double* r1a, double* q, double* r) __attribute__((always_inline)) {
         double grp[NGA * 4], Cp[NX * NU];
-        ldn(grp, C::C_GRP, NG * 4);
+        ldn(grp, C::L.C_GRP, NG * 4);
         load_cp(Cp);
         hold(grp, NG * 4);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            cst(C::C_R1A + g, r1a[g]);
+            cst(C::L.C_R1A + g, r1a[g]);
 #pragma unroll
             for (int i = 0; i < 3; ++i) r1[i] -= grp[g * 4 + i] * r1a[g];
         }
@@ -2551,8 +2067,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     // group directions: da_g = (r1a_g - Hpa_g' dp) / Haa_g
     auto recover_aux = [&](const double* dzl, double* da) __attribute__((always_inline)) {
         double grp[NGA * 4], r1a[NGA];
-        ldn(grp, C::C_GRP, NG * 4);
-        ldn(r1a, C::C_R1A, NG);
+        ldn(grp, C::L.C_GRP, NG * 4);
+        ldn(r1a, C::L.C_R1A, NG);
         hold(grp, NG * 4);
         hold(r1a, NG);
 #pragma unroll
@@ -2629,8 +2145,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     double wv[NQ], eta = 1.0, ltq[NQ], rcq[NQ];
     auto issue_soc = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) { wv[j] = cld(C::C_WV + j); ltq[j] = cld(C::C_LTQ + j); rcq[j] = cld(C::C_RCQ + j); }
-        eta = cld(C::C_ETA);
+        for (int j = 0; j < NQ; ++j) { wv[j] = cld(C::L.C_WV + j); ltq[j] = cld(C::L.C_LTQ + j); rcq[j] = cld(C::L.C_RCQ + j); }
+        eta = cld(C::L.C_ETA);
     };
     auto hold_soc = [&]() __attribute__((always_inline)) { hold(wv, NQ); hold(ltq, NQ); hold(rcq, NQ); hold(&eta, 1); };
     auto load_soc = [&]() __attribute__((always_inline)) {
@@ -2651,11 +2167,11 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         // C3: 12.3 -> ~5 IPM iterations on average.
         load_state();
         double wl[NR];
-        ldn(wl, C::C_WL, NR);
+        ldn(wl, C::L.C_WL, NR);
         hold(wl, NR);
         // the slack-relative dual floor, except in the classes with the stiff-facet stage system (the coupled double /
         // single integrators: there it lengthened the C4 tail; the twin the same)
-        const bool kfl = !(C::STF && has_coll);
+        const bool kfl = !(C::L.STF && has_coll);
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             double gz, h;
@@ -2689,18 +2205,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     // (CVXOPT coneqp initialisation; oracle/qp_dense.py does the same on the dense form)
         fresh();
         constexpr bool DSTRM = NX > 8;   // n = 12: the 264-double disc row is read per use, not held
-        double dt[DSTRM ? 1 : C::DSTR];
+        double dt[DSTRM ? 1 : C::L.DSTR];
         issue_state();
-        if constexpr (!DSTRM) ldn(dt, C::C_DT, C::DSTR);
+        if constexpr (!DSTRM) ldn(dt, C::L.C_DT, C::L.DSTR);
         hold_state();
-        if constexpr (!DSTRM) hold(dt, C::DSTR);
+        if constexpr (!DSTRM) hold(dt, C::L.DSTR);
 #pragma unroll
         for (int r = 0; r < NR; ++r) { s_set(r, 1.0); l_set(r, 0.0); }
         double Wu[NU * NU], rp[NX];
 #pragma unroll
         for (int e = 0; e < NU * NU; ++e) Wu[e] = (e / NU == e % NU) ? 1.0 : 0.0;
         dyn_residual(z, [&](int e) __attribute__((always_inline)) -> double {
-            if constexpr (DSTRM) return wld(qp_opaque(vt), (C::C_DT + e) * colb);
+            if constexpr (DSTRM) return wld(qp_opaque(vt), (C::L.C_DT + e) * colb);
             else return dt[e];
         }, rp);
         assemble(true, Wu, rp);
@@ -2722,13 +2238,13 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         set_boundary(z);
         if (!factor()) { status = SCVX_STATUS_NUMERICAL; fail_code = 1.0; }
         __syncthreads();  // factor columns (global) -> lane-parallel solve passes
-        double dz[NZ], dy[NX], da[NGA], dv0[NVA], dnv[NVA], rs0[C::PMA], fn0[C::PMA];
+        double dz[NZ], dy[NX], da[NGA], dv0[NVA], dnv[NVA], rs0[C::L.PMA], fn0[C::L.PMA];
         // virtual control at unit scaling from nu = e = 0: nu's rhs is 0 (the two rows cancel), e's is -w_nu
 #pragma unroll
         for (int i = 0; i < NVA; ++i) dv0[i] = 0.0;
         // (unit scaling: every facet folds, D = 1 is never stiff next to Rhat)
 #pragma unroll
-        for (int i = 0; i < C::PMA; ++i) rs0[i] = 0.0;
+        for (int i = 0; i < C::L.PMA; ++i) rs0[i] = 0.0;
         solve(q, rr, dv0, dz, dy, dnv, rs0, fn0);
         recover_aux(dz, da);
         load_state();
@@ -2806,8 +2322,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         constexpr bool ASTR = NX > 8;
         double Cpr[NX * NU], dA[ASTR ? 1 : NX * NX], dSz[2 * NX];
         issue_state();
-        if constexpr (!ASTR) ldn(dA, C::C_DT, NX * NX);
-        ldn(dSz, C::C_DT + NX * NX + 2 * NX * NU, 2 * NX);
+        if constexpr (!ASTR) ldn(dA, C::L.C_DT, NX * NX);
+        ldn(dSz, C::L.C_DT + NX * NX + 2 * NX * NU, 2 * NX);
         load_cp(Cpr);
         hold_state();
         if constexpr (!ASTR) hold(dA, NX * NX);
@@ -2908,7 +2424,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     double col[NX];
                     const int vo = qp_opaque(vt);
 #pragma unroll
-                    for (int i = 0; i < NX; ++i) col[i] = wld(vo, (C::C_DT + k * NX + i) * colb);
+                    for (int i = 0; i < NX; ++i) col[i] = wld(vo, (C::L.C_DT + k * NX + i) * colb);
 #pragma unroll
                     for (int i = 0; i < NX; ++i) rp[i] -= col[i] * z[k];
 #pragma unroll
@@ -2918,7 +2434,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         }
         {   // second chunk: B | C
             double dBC[2 * NX * NU];
-            ldn(dBC, C::C_DT + NX * NX, 2 * NX * NU);
+            ldn(dBC, C::L.C_DT + NX * NX, 2 * NX * NU);
             hold(dBC, 2 * NX * NU);
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
@@ -2975,7 +2491,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     for (int j = 0; j < NU; ++j) rd[NX + j] = 0.0;
                 }
 #pragma unroll
-                for (int i = 0; i < NZ; ++i) { dres = fmax(dres, fabs(rd[i])); cst(C::C_RD + i, rd[i]); }
+                for (int i = 0; i < NZ; ++i) { dres = fmax(dres, fabs(rd[i])); cst(C::L.C_RD + i, rd[i]); }
                 if (vact) {   // virtual control rows nu - e + s1 = 0, -nu - e + s2 = 0; rd = (-y + l1 - l2, w_nu - l1 - l2)
 #pragma unroll
                     for (int i = 0; i < NV; ++i) {
@@ -2987,8 +2503,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                         gap += vs[2 * i] * vl[2 * i] + vs[2 * i + 1] * vl[2 * i + 1];
                         const double rdn = -y[i] + vl[2 * i] - vl[2 * i + 1], rde = wnu - vl[2 * i] - vl[2 * i + 1];
                         dres = fmax(dres, fmax(fabs(rdn), fabs(rde)));
-                        cst(C::C_VRD + 2 * i, rdn);
-                        cst(C::C_VRD + 2 * i + 1, rde);
+                        cst(C::L.C_VRD + 2 * i, rdn);
+                        cst(C::L.C_VRD + 2 * i + 1, rde);
                         pobj += wnu * ve[i];
                     }
                 }
@@ -3086,8 +2602,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 }
         }
 #pragma unroll
-        for (int j = 0; j < NQ; ++j) { cst(C::C_WV + j, wv[j]); cst(C::C_LTQ + j, ltq[j]); cst(C::C_RCQ + j, rcq[j]); }
-        cst(C::C_ETA, eta);
+        for (int j = 0; j < NQ; ++j) { cst(C::L.C_WV + j, wv[j]); cst(C::L.C_LTQ + j, ltq[j]); cst(C::L.C_RCQ + j, rcq[j]); }
+        cst(C::L.C_ETA, eta);
         assemble(false, Wi2uu, rp);
         set_boundary(z);
         stamp(0);
@@ -3098,10 +2614,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         double sgmu = 0.0;
         double dz[NZ], dy[NX], da[NGA], dsq[NQ], dlq[NQ], cpv[NR];
         double dnv[NVA], dne[NVA], vcpv[2 * NVA];   // virtual control directions, predictor products
-        // stiff facets of this node's stage (C::STF): their indices (-1: empty slot) and multiplier steps
-        double sfr[C::PMA], fnu[C::PMA];
+        // stiff facets of this node's stage (C::L.STF): their indices (-1: empty slot) and multiplier steps
+        double sfr[C::L.PMA], fnu[C::L.PMA];
 #pragma unroll
-        for (int i = 0; i < C::PMA; ++i) { sfr[i] = -1.0; fnu[i] = 0.0; }
+        for (int i = 0; i < C::L.PMA; ++i) { sfr[i] = -1.0; fnu[i] = 0.0; }
         auto rco_of = [&](int r, bool corr) __attribute__((always_inline)) -> double {
             const double v = -s_(r) * l_(r);
             return corr ? v - cpv[r] + sgmu : v;
@@ -3125,18 +2641,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             fresh();
             issue_state();
             issue_soc();
-            ldn(r1, C::C_RD, NZ);
-            if (corr) ldn(cpv, C::C_CP, NR);
-            const bool sany = C::STF && stf_any();   // uniform: a stage of this factor kept a stiff facet
-            if constexpr (C::STF) if (sany) ldb(sfr, C::B_SF, C::PM);
+            ldn(r1, C::L.C_RD, NZ);
+            if (corr) ldn(cpv, C::L.C_CP, NR);
+            const bool sany = C::L.STF && stf_any();   // uniform: a stage of this factor kept a stiff facet
+            if constexpr (C::L.STF) if (sany) ldb(sfr, C::L.B_SF, C::L.PM);
             hold_state();
             hold_soc();
             hold(r1, NZ);
             if (corr) hold(cpv, NR);
-            if constexpr (C::STF) if (sany) hold(sfr, C::PM);
-            double rhs_s[C::PMA];
+            if constexpr (C::L.STF) if (sany) hold(sfr, C::L.PM);
+            double rhs_s[C::L.PMA];
 #pragma unroll
-            for (int i = 0; i < C::PMA; ++i) rhs_s[i] = 0.0;
+            for (int i = 0; i < C::L.PMA; ++i) rhs_s[i] = 0.0;
 #pragma unroll
             for (int i = 0; i < NZ; ++i) r1[i] = act ? -r1[i] : 0.0;
 #pragma unroll
@@ -3151,12 +2667,12 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     const double rcr = gz + s_(r) - h;
                     row_accA(r, -l_(r), r1a);  // -rd, group part: -(w_g - sum lambda)
                     double c = -qp_div(rco_of(r, corr) + l_(r) * rcr, s_(r));
-                    if constexpr (C::STF) {
-                        if (r < C::R_BOX) {   // a stiff facet: its rho = -(rco / l + rc) goes to the stage system
+                    if constexpr (C::L.STF) {
+                        if (r < C::L.R_BOX) {   // a stiff facet: its rho = -(rco / l + rc) goes to the stage system
                             const double rho_f = -(rco_of(r, corr) / l_(r) + rcr);
                             bool st = false;
 #pragma unroll
-                            for (int i = 0; i < C::PM; ++i) {
+                            for (int i = 0; i < C::L.PM; ++i) {
                                 const bool m_ = sfr[i] == (double)r;
                                 rhs_s[i] = m_ ? rho_f : rhs_s[i];
                                 st |= m_;
@@ -3186,7 +2702,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 for (int i = 0; i < NU; ++i) r1[NX + i] += w3[1 + i];
             }
 #pragma unroll
-            for (int j = 0; j < NQ; ++j) cst(C::C_RHO + j, rho[j]);
+            for (int j = 0; j < NQ; ++j) cst(C::L.C_RHO + j, rho[j]);
             double q[NX], rr[NU], dvl[NVA];
             reduce_rhs(r1, r1a, q, rr);
 #pragma unroll
@@ -3195,8 +2711,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 // rhs of (nu_i, e_i): -rd - sum_r G_r' (rco_r + l_r rc_r) / s_r, then e_i eliminated:
                 // nu's linear term -(r_nu - b/a r_e), a = D1 + D2, b = D2 - D1 (r_e kept for the recovery)
                 double vrd[2 * NV];
-                ldn(vrd, C::C_VRD, 2 * NV);
-                if (corr) ldn(vcpv, C::C_VCP, 2 * NV);
+                ldn(vrd, C::L.C_VRD, 2 * NV);
+                if (corr) ldn(vcpv, C::L.C_VCP, 2 * NV);
                 hold(vrd, 2 * NV);
                 if (corr) hold(vcpv, 2 * NV);
 #pragma unroll
@@ -3207,7 +2723,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     const double rn = -vrd[2 * i] + c1 - c2, re = -vrd[2 * i + 1] - c1 - c2;
                     const double d1 = qp_div(vl[2 * i], vs[2 * i]), d2 = qp_div(vl[2 * i + 1], vs[2 * i + 1]);
                     dvl[i] = vact ? -(rn - qp_div(d2 - d1, d1 + d2) * re) : 0.0;
-                    cst(C::C_VRE + i, re);
+                    cst(C::L.C_VRE + i, re);
                 }
             }
             stamp(2);
@@ -3216,8 +2732,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             fresh();
             issue_state();
             issue_soc();
-            if (corr) ldn(cpv, C::C_CP, NR);
-            ldn(rho, C::C_RHO, NQ);
+            if (corr) ldn(cpv, C::L.C_CP, NR);
+            ldn(rho, C::L.C_RHO, NQ);
             hold_state();
             hold_soc();
             if (corr) hold(cpv, NR);
@@ -3225,8 +2741,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             recover_aux(dz, da);
             if constexpr (NV > 0) {   // de = (r_e - b dnu) / a
                 double vre[NV];
-                ldn(vre, C::C_VRE, NV);
-                if (corr) ldn(vcpv, C::C_VCP, 2 * NV);
+                ldn(vre, C::L.C_VRE, NV);
+                if (corr) ldn(vcpv, C::L.C_VCP, 2 * NV);
                 hold(vre, NV);
                 if (corr) hold(vcpv, 2 * NV);
 #pragma unroll
@@ -3263,10 +2779,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             const double rcr = gz + s_(r) - h;
             dsr = -rcr - gd;
             dlr = qp_div(rco_of(r, corr) + l_(r) * (rcr + gd), s_(r));
-            if constexpr (C::STF) {
-                if (r < C::R_BOX) {   // a stiff facet's multiplier step comes from the stage system
+            if constexpr (C::L.STF) {
+                if (r < C::L.R_BOX) {   // a stiff facet's multiplier step comes from the stage system
 #pragma unroll
-                    for (int i = 0; i < C::PM; ++i) dlr = sfr[i] == (double)r ? fnu[i] : dlr;
+                    for (int i = 0; i < C::L.PM; ++i) dlr = sfr[i] == (double)r ? fnu[i] : dlr;
                 }
             }
         };
@@ -3294,7 +2810,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     q1 += fma(sr, dlr, lr * dsr);
                     q2 = fma(dsr, dlr, q2);
                     pr += 0.0 * (dsr + dlr);
-                    if (!corr) cst(C::C_CP + r, dsr * dlr);
+                    if (!corr) cst(C::L.C_CP + r, dsr * dlr);
                 }
             }
             if constexpr (NV > 0) {
@@ -3316,7 +2832,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                             q1 += fma(sr, dlr[k], lr * dsr[k]);
                             q2 = fma(dsr[k], dlr[k], q2);
                             pr += 0.0 * (dsr[k] + dlr[k]);
-                            if (!corr) cst(C::C_VCP + 2 * i + k, dsr[k] * dlr[k]);
+                            if (!corr) cst(C::L.C_VCP + 2 * i + k, dsr[k] * dlr[k]);
                         }
                     }
                 }
@@ -3454,8 +2970,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     load_state();
     // the warm-start state of the next solve: row duals and the initial / terminal multipliers
 #pragma unroll
-    for (int r = 0; r < NR; ++r) cst(C::C_WL + r, l_(r));
-    cst(C::C_WY, lane < 2 * NX ? lds[V_YI + lane] : 0.0);
+    for (int r = 0; r < NR; ++r) cst(C::L.C_WL + r, l_(r));
+    cst(C::L.C_WY, lane < 2 * NX ? lds[V_YI + lane] : 0.0);
     if (a.trace && agent == a.trace_agent && lane == 0) {
         double* dd = a.trace + 8 * a.trace_cap;
         dd[0] = 0.0; dd[1] = 0.0; dd[2] = (double)(__builtin_amdgcn_s_memtime() - cyc_all0);
@@ -3507,7 +3023,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 template <class C, int KC = 0>
 int qp_launch(const QPArgs& a, hipStream_t st) {
     if (KC > 0 && a.T.K != KC) return set_error(SCVX_EINVAL, "qp: K-specialised instantiation launched at another K");
-    const size_t lds = sizeof(double) * (size_t)C::lds_doubles(a.T.K);
+    const size_t lds = sizeof(double) * (size_t)C::L.lds_doubles(a.T.K);
     if (lds > 65536) (void)hipFuncSetAttribute((const void*)qp_ipm_kernel<C, KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((qp_ipm_kernel<C, KC>), dim3(a.N), dim3(WAVE), lds, st, a);
     return check_launch("qp_ipm_kernel");

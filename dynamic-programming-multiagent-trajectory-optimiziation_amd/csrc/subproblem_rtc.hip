@@ -24,21 +24,45 @@
 #include "common.hpp"
 #include "scvx_hip.h"
 #include "subproblem_rtc.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
-const char* const kQpIpm =
-#include "qp_ipm.inc"
-    ;
-const char* const kScpKernel =
-#include "scp_kernel.inc"
-    ;
-const char* const kWaveOps =
-#include "wave_ops.inc"
-    ;
-const char* const kScvxHdr =
-#include "scvx_hip_h.inc"
-    ;
+// every header the kernels include, as {include name, text} (the Makefile's RTC_HEADERS)
+struct Header {
+    const char* name;
+    const char* text;
+};
+const Header kHeaders[] = {
+    {"scvx_hip.h",
+#include "scvx_hip.h.inc"
+    },
+    {"wave_ops.hpp",
+#include "wave_ops.hpp.inc"
+    },
+    {"qp_consts.hpp",
+#include "qp_consts.hpp.inc"
+    },
+    {"qp_layout.hpp",
+#include "qp_layout.hpp.inc"
+    },
+    {"qp_access.hpp",
+#include "qp_access.hpp.inc"
+    },
+    {"qp_factor_phase.hpp",
+#include "qp_factor_phase.hpp.inc"
+    },
+    {"qp_ipm.hpp",
+#include "qp_ipm.hpp.inc"
+    },
+    {"scp_layout.hpp",
+#include "scp_layout.hpp.inc"
+    },
+    {"scp_kernel.hpp",
+#include "scp_kernel.hpp.inc"
+    },
+};
+constexpr int kNumHeaders = (int)(sizeof(kHeaders) / sizeof(kHeaders[0]));
 
 struct Instance {
     std::vector<char> code;
@@ -54,9 +78,9 @@ int compile(const std::string& key, const std::string& src, const std::string& e
     auto it = g_cache.find(key);
     if (it != g_cache.end()) { *out = it->second.get(); return SCVX_OK; }
     hiprtcProgram prog;
-    const char* hsrc[4] = {kQpIpm, kScpKernel, kWaveOps, kScvxHdr};
-    const char* hname[4] = {"qp_ipm.hpp", "scp_kernel.hpp", "wave_ops.hpp", "scvx_hip.h"};
-    if (hiprtcCreateProgram(&prog, src.c_str(), "scvx_subproblem_rtc.hip", 4, hsrc, hname) != HIPRTC_SUCCESS)
+    const char *hsrc[kNumHeaders], *hname[kNumHeaders];
+    for (int i = 0; i < kNumHeaders; ++i) { hsrc[i] = kHeaders[i].text; hname[i] = kHeaders[i].name; }
+    if (hiprtcCreateProgram(&prog, src.c_str(), "scvx_subproblem_rtc.hip", kNumHeaders, hsrc, hname) != HIPRTC_SUCCESS)
         return scvx::set_error(SCVX_EINVAL, "subproblem rtc: hiprtcCreateProgram failed");
     hiprtcAddNameExpression(prog, expr.c_str());
     const char* opts[] = {"--offload-arch=" SCVX_OFFLOAD_ARCH, "-O3", "-std=c++17"};
@@ -155,7 +179,7 @@ namespace scvx {
 
 int rtc_qp_launch(const QPArgs& a, int nb, int no, int nc, int vc, hipStream_t st) {
     const int nx = a.T.n_x, nu = a.T.n_u;
-    const size_t lds = sizeof(double) * (size_t)qp_lds_doubles(nx, nu, nb, no, nc, vc, a.T.K);
+    const size_t lds = sizeof(double) * (size_t)qp_layout(nx, nu, nb, no, nc, vc).lds_doubles(a.T.K);
     QPArgs copy = a;
     void* args[] = {&copy};
     return launch(qp_inst(nx, nu, nb, no, nc, vc), args, (unsigned)a.N, WAVE, lds, st);
@@ -176,8 +200,8 @@ extern "C" int scvx_rtc_subproblem_compile(int kind, const int* cls, int ncls, s
         return scvx::set_error(SCVX_EINVAL, "scvx_rtc_subproblem_compile: kind 0 takes 6 class ints, kind 1 takes 4");
     for (int i = 0; i < ncls; ++i)
         if (cls[i] < 0 || cls[i] > 64) return scvx::set_error(SCVX_EINVAL, "scvx_rtc_subproblem_compile: class out of range");
-    // the solve entry points' own limits (subproblem_rtc.hpp), checked before a ~10 s compile
-    const char* bad = kind == 0 ? scvx::rtc_qp_class_error(cls[0], cls[1], cls[2], cls[3], cls[4], cls[5], 2)
+    // the solve entry points' own limits (qp_layout.hpp, subproblem_rtc.hpp), checked before a ~10 s compile
+    const char* bad = kind == 0 ? scvx::qp_class_error(cls[0], cls[1], cls[2], cls[3], cls[4], cls[5], 2)
                                 : scvx::rtc_scp_class_error(cls[0], cls[1], cls[2]);
     if (bad) return scvx::set_error(SCVX_EUNSUPPORTED, bad);
     const Inst i = kind == 0 ? qp_inst(cls[0], cls[1], cls[2], cls[3], cls[4], cls[5])

@@ -16,6 +16,13 @@
 #include <vector>
 
 #include "../include/scvx_hip.h"
+// QP_WARM_ETA, QP_WARM_KAPPA, QP_STIFF, QP_TAU_END: the kernel's own definitions (csrc/, on the include path)
+#include "qp_consts.hpp"
+
+using scvx::QP_STIFF;
+using scvx::QP_TAU_END;
+using scvx::QP_WARM_ETA;
+using scvx::QP_WARM_KAPPA;
 
 namespace {
 
@@ -379,7 +386,7 @@ struct Riccati {
     std::vector<Mat> Pe, Pie;   // effective next-stage P~, Pi~ of stage t (= P_{t+1}, Pi_{t+1} without nu)
     // trust-region facets (the 2^m rows g_f'u <= h_f of ||u - ubar||_1 <= tr at nodes t < K-1), kept out of the
     // node Hessians: Df[t] their barrier weights lambda/s (empty: the stage has none).  Stage t folds D g g' of
-    // every facet into its input block Rh EXCEPT the stiff ones (D_f > STIFF_RATIO max diag of the rest, when
+    // every facet into its input block Rh EXCEPT the stiff ones (D_f > QP_STIFF max diag of the rest, when
     // 1 <= #stiff <= m-1), which stay explicit stage unknowns of the quasi-definite system
     //   [R0 G; G' -D^-1] [u; nu] = [-y; rho]
     // solved by the Woodbury identity Rh^-1 = R0^-1 - W C^-1 W', W = R0^-1 G, C = D^-1 + G'W (nu = the facets'
@@ -395,7 +402,6 @@ struct Riccati {
 
 // trust-region facet f's coefficient on input j (setup_agent's sign pattern)
 static inline double facet_g(int f, int j) { return ((f >> j) & 1) ? -1.0 : 1.0; }
-constexpr double STIFF_RATIO = 1e6;
 static bool stiff_enabled() {
     static int e = -1;
     if (e < 0) { const char* v = std::getenv("SCVX_TWIN_STIFF"); e = v ? std::atoi(v) : 1; }
@@ -511,21 +517,21 @@ static void riccati_factor(const Agent& ag, const std::vector<Mat>& H, Riccati& 
             const int nf = (int)Df.size();
             double dmax = 0.0;   // the stage's Rhat without the facets
             for (int j = 0; j < m; ++j) dmax = std::max(dmax, std::fabs(Rh(j, j)));
-            // stiff set (the kernel's rule, qp_ipm.hpp factor phase 3): the facets with D above STIFF_RATIO x the
+            // stiff set (the kernel's rule, qp_ipm.hpp factor phase 3): the facets with D above QP_STIFF x the
             // largest diagonal of the stage's Rhat without them, kept explicit when there are at most m-1 of them and no two are
             // opposite (a face or an edge of the L1 ball: they leave a complement whose small curvature the fold
             // would lose).  m or more (a vertex) make every direction of u stiff: the folded sum loses nothing
             // there, while the Woodbury form would cancel (measured on the C4 dumps: 407 -> 85 optimal of 444).
             std::vector<int> st;
-            // candidate nodes only (the kernel's assemble): some D_f above STIFF_RATIO x the largest diagonal of the
+            // candidate nodes only (the kernel's assemble): some D_f above QP_STIFF x the largest diagonal of the
             // node's own R (Rhat = R + Bt'P Bt >= R, so no other node can have a stiff facet); the kernel folds the
             // other nodes' facets into R before phase 2, the twin here -- the same sum in another rounding order
             double rdm = 0.0, dfm = 0.0;
             for (int j = 0; j < m; ++j) rdm = std::max(rdm, std::fabs(Rm(j, j)));
             for (int f = 0; f < nf; ++f) dfm = std::max(dfm, Df[f]);
-            if (stiff_enabled() && ag.T->j_max > 0 && n <= 8 && m >= 2 && m <= 4 && dfm > STIFF_RATIO * rdm) {
+            if (stiff_enabled() && ag.T->j_max > 0 && n <= 8 && m >= 2 && m <= 4 && dfm > QP_STIFF * rdm) {
                 for (int f = 0; f < nf; ++f)
-                    if (Df[f] > STIFF_RATIO * dmax) st.push_back(f);
+                    if (Df[f] > QP_STIFF * dmax) st.push_back(f);
                 bool opp = false;
                 for (size_t a = 0; a < st.size(); ++a)
                     for (size_t b = a + 1; b < st.size(); ++b) opp = opp || ((st[a] ^ st[b]) == nf - 1);
@@ -959,9 +965,7 @@ static bool init_point(Agent& ag) {
 // 5.1 IPM iterations on average, the same optima to the stopping tolerance.
 // Per-agent state: per node z (nv) | lambda (nr) | lsoc (m+1), padded to a fixed stride, then y ((K-1) n),
 // y_init (n), y_fin (n).
-constexpr double QP_WARM_ETA = 1e-3;
-// a row's dual floor: min(QP_WARM_ETA, QP_WARM_KAPPA / s) (round 6; kernel csrc/qp_ipm.hpp, the same constants)
-constexpr double QP_WARM_KAPPA = 1e-5;
+// a row's dual floor: min(QP_WARM_ETA, QP_WARM_KAPPA / s) (round 6; csrc/qp_consts.hpp, shared with the kernel)
 static int warm_node_stride(const scvx_qp_template* T) {
     const int n = T->n_x, m = T->n_u, nnu = T->w_nu > 0.0 ? n : 0;
     const int aux = T->n_obs + (T->j_max > 0 ? 1 : 0) + nnu;
@@ -1503,7 +1507,7 @@ static int solve_agent(Agent& ag, int& iters_out, double& obj_out, const double*
             // step fraction (kernel: the same rule, QP_TAU_END): 0.99 of the way to the boundary, 1 - 1e-5 once
             // the affine predictor takes a (nearly) full step -- the end game, where the fraction alone caps
             // the gap reduction per iteration at 1 / (1 - fraction).  SCVX_TAU_END: experiment knob
-            static const double tau_end = std::getenv("SCVX_TAU_END") ? std::atof(std::getenv("SCVX_TAU_END")) : 0.99999;
+            static const double tau_end = std::getenv("SCVX_TAU_END") ? std::atof(std::getenv("SCVX_TAU_END")) : QP_TAU_END;
             static const double tau_aa = std::getenv("SCVX_TAU_AA") ? std::atof(std::getenv("SCVX_TAU_AA")) : 0.99;  // knob
             static const double tau_mid = std::getenv("SCVX_TAU_MID") ? std::atof(std::getenv("SCVX_TAU_MID")) : 0.99;  // knob
             const double eta = (aa >= tau_aa) ? tau_end : tau_mid;
