@@ -355,20 +355,49 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         if (lane < 16) lds[V_ST + lane] = 0.0;
     }
     // C_{t-1} (column-major as disc) of this node, from the transposed disc of node t-1 (the lane below)
-    auto load_cp = [&](double* Cp) __attribute__((always_inline)) {
+    // (issue_cp / take_cp: the loads with a phase's batch, the hold and the t = 0 mask at the first use)
+    auto issue_cp = [&](double* Cp) __attribute__((always_inline)) {
 #pragma unroll
         for (int e = 0; e < NX * NU; ++e) Cp[e] = wld(vcur - 8, (C::L.C_DT + NX * NX + NX * NU + e) * colb);
+    };
+    auto take_cp = [&](double* Cp) __attribute__((always_inline)) {
         hold(Cp, NX * NU);
 #pragma unroll
         for (int e = 0; e < NX * NU; ++e) Cp[e] = (t > 0) ? Cp[e] : 0.0;
     };
+    auto load_cp = [&](double* Cp) __attribute__((always_inline)) {
+        issue_cp(Cp);
+        take_cp(Cp);
+    };
+    // Workspace round trips of an IPM iteration merged or hidden (DESIGN §3.3 "Workspace round trips"); only where
+    // loads are issued changes, never a floating-point expression.  Only the classes with n <= 8, at most 8 soft rows
+    // and no virtual control (RT_ON): the n = 12 classes interleave their loads with the uses (hold is a no-op there),
+    // and they, the 48-row classes and the virtual-control classes spill already -- these steps raised their scratch.
+    // They keep the one-batch-per-use form, with every load target declared where it is used (the arrays below that
+    // a step moves to an outer scope have one element there).
+    //   RT_A  the corrector's Newton rhs runs on the node state, the SOC scaling and the predictor products that are
+    //         live from the predictor's step length (no sweep lies in between); its C_RD is loaded with the
+    //         predictor's post-solve batch
+    //   RT_B  one load batch per node phase: the group factors, C_{t-1} and r1a are issued with the phase's batch
+    //   RT_C  the solve passes' operands are issued before the chain that precedes them (after the chain's own batch)
+    //   RT_F  the predictor's rhs batch is issued inside the factor, behind the loads of the chunk transition matrices,
+    //         and is in flight across their products
+    // (diagnostics builds: -DQP_RT_STEPS=<bits A = 1, B = 2, C = 4, F = 8> builds the steps alone, tools/build_variant.sh)
+#ifndef QP_RT_STEPS
+#define QP_RT_STEPS 15
+#endif
+    constexpr bool RT_ON = NX <= 8 && NS <= 8 && NV == 0;
+    constexpr bool RT_A = RT_ON && (QP_RT_STEPS & 1), RT_B = RT_ON && (QP_RT_STEPS & 2),
+                   RT_C = RT_ON && (QP_RT_STEPS & 4), RT_F = RT_ON && (QP_RT_STEPS & 8);
 
     // ------------------------------------------------------------------ factor sweep
     // Stage inputs (Q, S, R, e of the node phase; A, Bt, C_{t-1}) are in packet t; Acl goes to
     // LDS, the other outputs to the stage-minor columns, M (and its LU) / Pi_0 / xe to persistent
     // LDS.  false on a breakdown.
     constexpr int PFN = (PKT + WAVE - 1) / WAVE;
-    auto factor = [&]() __attribute__((always_inline)) -> bool {
+    // phi_issue(): called once the sweep is done, after the operand batch of the chunk transition matrices (RT_F: the
+    // predictor's rhs batch goes out there, in flight across the chunk products)
+    auto factor = [&](auto phi_issue) __attribute__((always_inline)) -> bool {
         // phase descriptors (rebuilt per call: nothing of them stays live outside the sweep)
         constexpr int E1 = 2 * NX * NX + 2 * NX * NU + 2 * NX, E2 = NX * NX + NU * NX + NU * NU, E4 = 4 * NX * NX;
         constexpr int R1 = (E1 + WAVE - 1) / WAVE, R2 = (E2 + WAVE - 1) / WAVE, R4 = (E4 + WAVE - 1) / WAVE;
@@ -1116,6 +1145,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     else ar[j][k] = wld(vo, FBB, k * 8);
                 }
             }
+            phi_issue();
 #pragma unroll
             for (int c = 0; c < NX; ++c) ph[c] = (c == ce) ? 1.0 : 0.0;
 #pragma unroll
@@ -1204,6 +1234,32 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         }
         wsync();
         stamp(4);
+        // Operands of the lane-parallel passes behind the chains (factor blocks and columns written long before).
+        // RT_C: issued ahead of the chain that precedes the pass, after the chain's own operand batch (loads return
+        // in order: the chain's first wait then does not cover them), unconditionally (a lane without a node reads
+        // out of range: 0) and pinned only at the first use, so the round trip overlaps the chain.
+        constexpr int HC = RT_C ? 1 : 0;   // (hoisted arrays: full size with RT_C, one element otherwise)
+        double hU[HC * NX + 1 - HC], hBt[HC * NX * NU + 1 - HC], hLd[HC * NU * NU + 1 - HC], hW2[HC * NU * NX + 1 - HC];
+        double hKap[HC * NU * NX + 1 - HC], hPi[HC * NX * NX + 1 - HC], hEv[HC * NX + 1 - HC];
+        double hKt[HC * NU * NX + 1 - HC], hP[HC * NX * NX + 1 - HC], hCp[HC * NX * NU + 1 - HC];
+        auto issue_bpost = [&](double* uu, double* Bt, double* Ld, double* W2) __attribute__((always_inline)) {
+            ldb(uu, C::L.B_U, NX);
+            ldn(Bt, C::L.C_BT, NX * NU);
+            ldb(Ld, C::L.B_LD, NU * NU);
+            ldb(W2, C::L.B_W2, NU * NX);
+        };
+        auto issue_fpre = [&](double* kap, double* Pi, double* Bt, double* ev) __attribute__((always_inline)) {
+            ldb(kap, C::L.B_KAP, NU * NX);
+            ldb(Pi, C::L.B_PI, NX * NX);
+            if (Bt) ldn(Bt, C::L.C_BT, NX * NU);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) ev[i] = pld(C::L.gE + i);
+        };
+        auto issue_fpost = [&](double* Kt, double* P, double* Cp) __attribute__((always_inline)) {
+            ldb(Kt, C::L.B_K, NU * NX);
+            ldb(P, C::L.B_P, NX * NX);
+            issue_cp(Cp);
+        };
         if constexpr (C::L.CHK) {
             const ChunkC cc = chunk_coords();
             const int ce = cc.ce, cs0 = cc.cs0, cs1 = cc.cs1;
@@ -1225,6 +1281,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 for (int k = 0; k < NX; ++k) ac[j][k] = wld(vo, FBB, k * NX * 8);
                 gc[j] = lds[V_G + (ok ? tj : 0) * NX + (ce < NX ? ce : 0)];
             }
+            if constexpr (RT_C) issue_bpost(hU, hBt, hLd, hW2);
             auto chainT = [&](double q, const double* a, double g) __attribute__((always_inline)) -> double {
                 double v0 = g, v1 = 0.0;
 #pragma unroll
@@ -1327,12 +1384,12 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         for (int i = 0; i < NX; ++i) { xa[i] = 0.0; pv[i] = 0.0; }
 #pragma unroll
         for (int j = 0; j < NU; ++j) k0[j] = 0.0;
+        // (RT_C: the forward pre-pass's operands in flight across this pass and the terminal solve; it keeps Bt)
+        if constexpr (RT_C) issue_fpre(hKap, hPi, nullptr, hEv);
         if (act) {
-            double uu[NX], Bt[NX * NU], Ld[NU * NU], W2[NU * NX];
-            ldb(uu, C::L.B_U, NX);
-            ldn(Bt, C::L.C_BT, NX * NU);
-            ldb(Ld, C::L.B_LD, NU * NU);
-            ldb(W2, C::L.B_W2, NU * NX);
+            double uul[NX * (1 - HC) + HC], Btl[NX * NU * (1 - HC) + HC], Ldl[NU * NU * (1 - HC) + HC], W2l[NU * NX * (1 - HC) + HC];
+            double *uu = RT_C ? hU : uul, *Bt = RT_C ? hBt : Btl, *Ld = RT_C ? hLd : Ldl, *W2 = RT_C ? hW2 : W2l;
+            if constexpr (!RT_C) issue_bpost(uu, Bt, Ld, W2);
             hold(uu, NX); hold(Bt, NX * NU); hold(Ld, NU * NU); hold(W2, NU * NX);
 #pragma unroll
             for (int i = 0; i < NX; ++i) pv[i] = lds[V_CH + t * NX + i];
@@ -1461,12 +1518,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int j = 0; j < NU; ++j) v0[j] = k0[j];
         if (act) {
-            double kap[NU * NX], Pi[NX * NX], Bt[NX * NU], ev[NX];
-            ldb(kap, C::L.B_KAP, NU * NX);
-            ldb(Pi, C::L.B_PI, NX * NX);
-            ldn(Bt, C::L.C_BT, NX * NU);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) ev[i] = pld(C::L.gE + i);
+            double kapl[NU * NX * (1 - HC) + HC], Pil[NX * NX * (1 - HC) + HC], Btl[NX * NU * (1 - HC) + HC], evl[NX * (1 - HC) + HC];
+            double *kap = RT_C ? hKap : kapl, *Pi = RT_C ? hPi : Pil, *Bt = RT_C ? hBt : Btl, *ev = RT_C ? hEv : evl;
+            if constexpr (!RT_C) issue_fpre(kap, Pi, Bt, ev);
             hold(kap, NU * NX); hold(Pi, NX * NX); hold(Bt, NX * NU); hold(ev, NX);
 #pragma unroll
             for (int i = 0; i < NU; ++i)
@@ -1534,6 +1588,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 }
                 fr[j] = lds[V_G + (ok ? tj : 0) * NX + (ce < NX ? ce : 0)];
             }
+            if constexpr (RT_C) issue_fpost(hKt, hP, hCp);
             auto chainF = [&](double x, const double* a, double f) __attribute__((always_inline)) -> double {
                 double w0 = f, w1 = 0.0;
 #pragma unroll
@@ -1635,10 +1690,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int i = 0; i < NV; ++i) dno[i] = 0.0;
         if (act) {
-            double xi[NX], Cp[NX * NU], Kt[NU * NX], P[NX * NX];
-            ldb(Kt, C::L.B_K, NU * NX);
-            ldb(P, C::L.B_P, NX * NX);
-            load_cp(Cp);
+            double xi[NX], Cpl[NX * NU * (1 - HC) + HC], Ktl[NU * NX * (1 - HC) + HC], Pl[NX * NX * (1 - HC) + HC];
+            double *Cp = RT_C ? hCp : Cpl, *Kt = RT_C ? hKt : Ktl, *P = RT_C ? hP : Pl;
+            if constexpr (!RT_C) issue_fpost(Kt, P, Cp);
+            take_cp(Cp);
             hold(Kt, NU * NX); hold(P, NX * NX);
 #pragma unroll
             for (int i = 0; i < NX; ++i) xi[i] = lds[V_CH + t * NX + i];
@@ -1864,7 +1919,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 
     // Node Hessian (row scaling D_r = l/s or 1, SOC block Wi2uu) -> packet Q, S, R (xi/u
     // coordinates); group elimination factors -> columns C_GRP.  Also writes e = -rp.
-    auto assemble = [&](bool unit, const double* Wi2uu, const double* rp) __attribute__((always_inline)) {
+    // (Cp: C_{t-1}; RT_B: issued by the caller with issue_cp, ahead of the arithmetic that precedes its use)
+    auto assemble = [&](bool unit, const double* Wi2uu, const double* rp, double* Cpx) __attribute__((always_inline)) {
         double dbox[NX], Hpp[3][3], Huu[NU * NU], Dfc[C::L.STF ? C::L.NTR : 1];
 #pragma unroll
         for (int i = 0; i < NX; ++i) dbox[i] = 2.0 * (wfs + wpx);
@@ -1944,8 +2000,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             const double d1 = unit ? 1.0 : qp_div(vl[2 * i], vs[2 * i]), d2 = unit ? 1.0 : qp_div(vl[2 * i + 1], vs[2 * i + 1]);
             pst(C::L.gD + i, vact ? qp_div(4.0 * d1 * d2, d1 + d2) : 1.0);
         }
-        double Q[NX * NX], Cp[NX * NU];
-        load_cp(Cp);
+        double Q[NX * NX], Cpl[RT_B ? 1 : NX * NU];
+        double* Cp = RT_B ? Cpx : Cpl;
+        if constexpr (!RT_B) issue_cp(Cp);
+        take_cp(Cp);
 #pragma unroll
         for (int i = 0; i < NX; ++i)
 #pragma unroll
@@ -2039,10 +2097,16 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     };
     // eliminate the group part of a Newton rhs (stores it for recover_aux): r1_p -= Hpa/Haa r1a;
     // returns the (xi, u) linear terms q, r of the node
-    auto reduce_rhs = [&](double* r1, const double* r1a, double* q, double* r) __attribute__((always_inline)) {
-        double grp[NGA * 4], Cp[NX * NU];
+    // (RT_B: the group factors and C_{t-1} come from the caller, issued by reduce_issue with the phase's batch)
+    auto reduce_issue = [&](double* grp, double* Cp) __attribute__((always_inline)) {
         ldn(grp, C::L.C_GRP, NG * 4);
-        load_cp(Cp);
+        issue_cp(Cp);
+    };
+    auto reduce_rhs = [&](double* r1, const double* r1a, double* q, double* r, double* grpx, double* Cpx) __attribute__((always_inline)) {
+        double grpl[RT_B ? 1 : NGA * 4], Cpl[RT_B ? 1 : NX * NU];
+        double *grp = RT_B ? grpx : grpl, *Cp = RT_B ? Cpx : Cpl;
+        if constexpr (!RT_B) reduce_issue(grp, Cp);
+        take_cp(Cp);
         hold(grp, NG * 4);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
@@ -2065,10 +2129,15 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         }
     };
     // group directions: da_g = (r1a_g - Hpa_g' dp) / Haa_g
-    auto recover_aux = [&](const double* dzl, double* da) __attribute__((always_inline)) {
-        double grp[NGA * 4], r1a[NGA];
+    // (RT_B: grp, r1a come from the caller, issued by aux_issue with the post-solve batch)
+    auto aux_issue = [&](double* grp, double* r1a) __attribute__((always_inline)) {
         ldn(grp, C::L.C_GRP, NG * 4);
         ldn(r1a, C::L.C_R1A, NG);
+    };
+    auto recover_aux = [&](const double* dzl, double* da, double* grpx, double* r1ax) __attribute__((always_inline)) {
+        double grpl[RT_B ? 1 : NGA * 4], r1al[RT_B ? 1 : NGA];
+        double *grp = RT_B ? grpx : grpl, *r1a = RT_B ? r1ax : r1al;
+        if constexpr (!RT_B) aux_issue(grp, r1a);
         hold(grp, NG * 4);
         hold(r1a, NG);
 #pragma unroll
@@ -2219,7 +2288,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             if constexpr (DSTRM) return wld(qp_opaque(vt), (C::L.C_DT + e) * colb);
             else return dt[e];
         }, rp);
-        assemble(true, Wu, rp);
+        double Cpa[RT_B ? NX * NU : 1];
+        if constexpr (RT_B) issue_cp(Cpa);
+        assemble(true, Wu, rp, Cpa);
         double r1[NZ], r1a[NGA];
 #pragma unroll
         for (int i = 0; i < NX; ++i) r1[i] = tsoft ? -2.0 * wfs * (z[i] - a.x_final[agent * NX + i]) : 0.0;
@@ -2233,10 +2304,11 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             row_eval(r, z, av, gz, h);
             if (row_on(r)) row_accT(r, -(gz - h), r1, r1a);
         }
-        double q[NX], rr[NU];
-        reduce_rhs(r1, r1a, q, rr);
+        double q[NX], rr[NU], grp0[RT_B ? NGA * 4 : 1], Cp0[RT_B ? NX * NU : 1];
+        if constexpr (RT_B) reduce_issue(grp0, Cp0);
+        reduce_rhs(r1, r1a, q, rr, grp0, Cp0);
         set_boundary(z);
-        if (!factor()) { status = SCVX_STATUS_NUMERICAL; fail_code = 1.0; }
+        if (!factor([]() {})) { status = SCVX_STATUS_NUMERICAL; fail_code = 1.0; }
         __syncthreads();  // factor columns (global) -> lane-parallel solve passes
         double dz[NZ], dy[NX], da[NGA], dv0[NVA], dnv[NVA], rs0[C::L.PMA], fn0[C::L.PMA];
         // virtual control at unit scaling from nu = e = 0: nu's rhs is 0 (the two rows cancel), e's is -w_nu
@@ -2246,7 +2318,11 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int i = 0; i < C::L.PMA; ++i) rs0[i] = 0.0;
         solve(q, rr, dv0, dz, dy, dnv, rs0, fn0);
-        recover_aux(dz, da);
+        {
+            double r1b[RT_B ? NGA : 1];
+            if constexpr (RT_B) aux_issue(grp0, r1b);
+            recover_aux(dz, da, grp0, r1b);
+        }
         load_state();
 #pragma unroll
         for (int i = 0; i < NZ; ++i) z[i] += act ? dz[i] : 0.0;
@@ -2558,6 +2634,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             double* tr_ = a.trace + 8 * it;
             tr_[0] = pres; tr_[1] = dres; tr_[2] = gap; tr_[3] = pobj * osc; tr_[7] = mu;
         }
+        // assemble's C_{t-1}: in flight across the scaling arithmetic (the residual phase's copy is dead by now)
+        double Cpa[RT_B ? NX * NU : 1];
+        if constexpr (RT_B) issue_cp(Cpa);
         // SOC Nesterov-Todd scaling (hyperbolic-rotation form, W lam = W^-1 s)
         double Wi2uu[NU * NU];
 #pragma unroll
@@ -2604,16 +2683,30 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) { cst(C::L.C_WV + j, wv[j]); cst(C::L.C_LTQ + j, ltq[j]); cst(C::L.C_RCQ + j, rcq[j]); }
         cst(C::L.C_ETA, eta);
-        assemble(false, Wi2uu, rp);
+        assemble(false, Wi2uu, rp, Cpa);
         set_boundary(z);
         stamp(0);
-        if (!factor()) { status = near ? SCVX_STATUS_MAX_ITER : SCVX_STATUS_NUMERICAL; fail_code = lds[V_FLAG]; break; }
+        // the Newton rhs's load targets (RT_F: the predictor's batch is issued inside the factor, behind its last loads)
+        double r1f[RT_F ? NZ : 1], grpf[RT_F && RT_B ? NGA * 4 : 1], Cpf[RT_F && RT_B ? NX * NU : 1];
+        auto rhs_batch = [&]() __attribute__((always_inline)) {
+            fresh();
+            issue_state();
+            issue_soc();
+            ldn(r1f, C::L.C_RD, NZ);
+            if constexpr (RT_B) reduce_issue(grpf, Cpf);
+        };
+        bool fok;
+        if constexpr (RT_F) fok = factor(rhs_batch);
+        else fok = factor([]() {});
+        if (!fok) { status = near ? SCVX_STATUS_MAX_ITER : SCVX_STATUS_NUMERICAL; fail_code = lds[V_FLAG]; break; }
         stamp(1);
 
         // complementarity rhs of row r: predictor -s l ; corrector -s l - ds_a dl_a + sigma mu
         double sgmu = 0.0;
         double dz[NZ], dy[NX], da[NGA], dsq[NQ], dlq[NQ], cpv[NR];
         double dnv[NVA], dne[NVA], vcpv[2 * NVA];   // virtual control directions, predictor products
+        // RT_A: the corrector's C_RD, loaded with the predictor's post-solve batch
+        double r1c[RT_A ? NZ : 1];
         // stiff facets of this node's stage (C::L.STF): their indices (-1: empty slot) and multiplier steps
         double sfr[C::L.PMA], fnu[C::L.PMA];
 #pragma unroll
@@ -2637,19 +2730,32 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         };
         // Newton direction for the complementarity rhs (rows: rco_of, SOC: rcq2); directions out
         auto newton = [&](bool corr, const double* rcq2) __attribute__((always_inline)) {
-            double r1[NZ], r1a[NGA], rho[NQ];
-            fresh();
-            issue_state();
-            issue_soc();
-            ldn(r1, C::L.C_RD, NZ);
-            if (corr) ldn(cpv, C::L.C_CP, NR);
+            double r1a[NGA], rho[NQ], r1l[RT_F ? 1 : NZ], grpl[RT_B && !RT_F ? NGA * 4 : 1], Cpl[RT_B && !RT_F ? NX * NU : 1];
+            double *r1 = RT_F ? r1f : r1l, *grp = RT_F ? grpf : grpl, *Cp = RT_F ? Cpf : Cpl;
+            // RT_A, corrector: the state, the SOC scaling, the predictor products (cpv: max_step(false)), the
+            // stiff-facet slots and r1c are live in registers -- the same values the reload returned
+            const bool live = RT_A && corr;
+            const bool pre = RT_F && !corr;   // rhs_batch went out inside the factor
+            if (!pre) fresh();
+            if (!live && !pre) {
+                issue_state();
+                issue_soc();
+                ldn(r1, C::L.C_RD, NZ);
+                if (corr) ldn(cpv, C::L.C_CP, NR);
+            }
+            if constexpr (RT_B) { if (!pre) reduce_issue(grp, Cp); }
             const bool sany = C::L.STF && stf_any();   // uniform: a stage of this factor kept a stiff facet
-            if constexpr (C::L.STF) if (sany) ldb(sfr, C::L.B_SF, C::L.PM);
-            hold_state();
-            hold_soc();
-            hold(r1, NZ);
-            if (corr) hold(cpv, NR);
-            if constexpr (C::L.STF) if (sany) hold(sfr, C::L.PM);
+            if (!live) {
+                if constexpr (C::L.STF) if (sany) ldb(sfr, C::L.B_SF, C::L.PM);
+                hold_state();
+                hold_soc();
+                hold(r1, NZ);
+                if (corr) hold(cpv, NR);
+                if constexpr (C::L.STF) if (sany) hold(sfr, C::L.PM);
+            } else {
+#pragma unroll
+                for (int i = 0; i < NZ; ++i) r1[i] = r1c[RT_A ? i : 0];
+            }
             double rhs_s[C::L.PMA];
 #pragma unroll
             for (int i = 0; i < C::L.PMA; ++i) rhs_s[i] = 0.0;
@@ -2704,7 +2810,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
             for (int j = 0; j < NQ; ++j) cst(C::L.C_RHO + j, rho[j]);
             double q[NX], rr[NU], dvl[NVA];
-            reduce_rhs(r1, r1a, q, rr);
+            reduce_rhs(r1, r1a, q, rr, grp, Cp);
 #pragma unroll
             for (int i = 0; i < NVA; ++i) dvl[i] = 0.0;
             if constexpr (NV > 0) {
@@ -2727,18 +2833,22 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 }
             }
             stamp(2);
-            solve(q, rr, dvl, dz, dy, dnv, rhs_s, fnu);
             // post-solve: group and SOC directions (state reloaded: nothing crossed the sweeps)
+            solve(q, rr, dvl, dz, dy, dnv, rhs_s, fnu);
+            double r1b[RT_B ? NGA : 1];
             fresh();
             issue_state();
             issue_soc();
             if (corr) ldn(cpv, C::L.C_CP, NR);
             ldn(rho, C::L.C_RHO, NQ);
+            if constexpr (RT_B) aux_issue(grp, r1b);
+            if constexpr (RT_A) { if (!corr) ldn(r1c, C::L.C_RD, NZ); }
             hold_state();
             hold_soc();
             if (corr) hold(cpv, NR);
             hold(rho, NQ);
-            recover_aux(dz, da);
+            if constexpr (RT_A) { if (!corr) hold(r1c, NZ); }
+            recover_aux(dz, da, grp, r1b);
             if constexpr (NV > 0) {   // de = (r_e - b dnu) / a
                 double vre[NV];
                 ldn(vre, C::L.C_VRE, NV);
@@ -2810,7 +2920,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                     q1 += fma(sr, dlr, lr * dsr);
                     q2 = fma(dsr, dlr, q2);
                     pr += 0.0 * (dsr + dlr);
-                    if (!corr) cst(C::L.C_CP + r, dsr * dlr);
+                    if constexpr (RT_A) {
+                        if (!corr) {
+                            // (the product pinned: kept in a register for the corrector's rhs it must stay the rounded
+                            // product that the store holds, not contract into the rhs's subtraction)
+                            double pp = dsr * dlr;
+                            hold(&pp, 1);
+                            cpv[r] = pp;
+                            cst(C::L.C_CP + r, pp);
+                        }
+                    } else {
+                        if (!corr) cst(C::L.C_CP + r, dsr * dlr);
+                    }
                 }
             }
             if constexpr (NV > 0) {
