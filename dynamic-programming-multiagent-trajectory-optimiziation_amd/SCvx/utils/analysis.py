@@ -1,0 +1,125 @@
+"""Multi-agent trajectory analysis -- drop-in for the reference SCvx/utils/analysis.py, computed on the GPU.
+
+Same functions and arguments, numpy in and numpy out: `min_inter_agent_distance` (:10-31),
+`min_agent_obstacle_distance` (:34-62), `compute_intersample_clearance` (:64-104).  The pairwise and
+obstacle minima run in scvx_pair_min_distance_batched / scvx_obstacle_min_distance_batched instead of the
+reference's Python double loop; the dense roll-outs in scvx_rollout_dense_batched.
+
+Added here (no reference counterpart): `min_inter_agent_separation_continuous`, the closest approach of
+any two agents BETWEEN the nodes as well as at them (scvx_hip.fleet_separation).
+"""
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+import scvx_hip
+from SCvx.discretization.first_order_hold import FirstOrderHold, builtin_model
+
+
+def _stack(X_list, device):
+    """[(n, K)] * N -> device tensor (N, K, n)."""
+    import torch
+    X = np.ascontiguousarray(np.stack([np.asarray(x, float).T for x in X_list]))
+    return torch.as_tensor(X, dtype=torch.float64, device=device)
+
+
+def min_inter_agent_distance(X_list: List[np.ndarray], device="cuda") -> Tuple[float, np.ndarray]:
+    """(d_min_global, d_mat): d_mat[i, j] = min_k ||X_i[0:3, k] - X_j[0:3, k]|| (rows 0:3 of whatever state is
+    given, as the reference), symmetric with a zero diagonal; d_min_global = the minimum over the strictly
+    positive entries (ValueError when there are none, as numpy's empty .min())."""
+    d_mat = scvx_hip.pair_min_distance(_stack(X_list, device)).cpu().numpy()
+    return d_mat[d_mat > 0].min(), d_mat
+
+
+def min_agent_obstacle_distance(X_list: List[np.ndarray], obstacles: Sequence, robot_radius: float,
+                                device="cuda") -> Tuple[float, np.ndarray]:
+    """(d_min_global, d_mat): d_mat[i, j] = min_k (||p_i(k) - c_j|| - (robot_radius + r_j)) over rows 0:3;
+    d_min_global its minimum (negative when penetrating)."""
+    d_mat = scvx_hip.obstacle_min_distance(_stack(X_list, device), list(obstacles), robot_radius).cpu().numpy()
+    return d_mat.min(), d_mat
+
+
+def compute_intersample_clearance(X: np.ndarray, U: np.ndarray, foh, obs_center: np.ndarray, obs_radius: float,
+                                  robot_radius: float, margin: float, resolution: int = 50):
+    """(tau_cont, h_cont, tau_disc, h_disc): obstacle clearance between and at the nodes of one trajectory.
+
+    This is the behaviour the reference's docstring documents, not the reference's code, which cannot run (it
+    calls the three-argument segment roll-out with one argument, analysis.py:90-92): per segment k the samples
+    tau = k + t, t in linspace(0, 1, resolution, endpoint=False), of the roll-out from X[:, k] under the FOH input
+    at sigma = 1; clearance = ||x[:len(obs_center)] - obs_center|| - (obs_radius + robot_radius + margin) on the
+    first len(obs_center) states.  h_disc is the same clearance at the K nodes.
+
+    The roll-outs are scvx_hip.rollout_dense calls on chunks of at most 16 samples (its limit): chunk c of every
+    segment starts from the segment's state at its first sample (one integrate_nonlinear roll-out from the node)
+    and is sampled at the trajectory's own FOH input restricted to the chunk."""
+    import torch
+    X, U = np.asarray(X, float), np.asarray(U, float)
+    model = builtin_model(foh.model, "compute_intersample_clearance")
+    dev = getattr(foh, "_device", "cuda")
+    params = getattr(foh.model, "scvx_params", None)
+    K, res = X.shape[1], int(resolution)
+    c = np.asarray(obs_center, float).reshape(-1)
+    pd = c.size
+    if not 1 <= pd <= min(3, X.shape[0]) or res < 1:
+        raise ValueError("compute_intersample_clearance: obs_center of 1..3 coordinates and resolution >= 1 expected")
+    total_radius = obs_radius + robot_radius + margin
+    dtp, nsub = foh.dt * 1.0, foh.rollout_nsub(1.0)
+    x0, u0, u1 = X[:, :-1].T, U[:, :-1].T, U[:, 1:].T   # (K-1, n), (K-1, m): one virtual agent per segment
+
+    def dev_t(a):
+        return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=dev)
+
+    pos = np.empty((K - 1, res, pd))
+    for i0 in range(0, res, 16):
+        cnt = min(16, res - i0)
+        t0, t1 = i0 / res, (i0 + cnt) / res
+        ua, ub = u0 + t0 * (u1 - u0), u0 + t1 * (u1 - u0)
+        xs = x0
+        if i0:   # the segments' states at t0: a one-interval roll-out over [0, t0 dt] whose end input is u(t0)
+            out = scvx_hip.integrate_nonlinear(model, dev_t(np.stack([x0, x0], 1)), dev_t(np.stack([u0, ua], 1)),
+                                               dev_t(np.full(K - 1, t0 * dtp)), True, nsub=nsub, params=params)
+            xs = out[:, 1].cpu().numpy()
+        P, _ = scvx_hip.rollout_dense(model, dev_t(np.stack([xs, xs], 1)), dev_t(np.stack([ua, ub], 1)),
+                                      dev_t(np.full(K - 1, (t1 - t0) * dtp)), S=cnt, nsub=nsub, pos_dim=pd,
+                                      params=params)
+        pos[:, i0:i0 + cnt] = P[:, 0, :cnt, :pd].cpu().numpy()
+    t = np.linspace(0, 1, res, endpoint=False)
+    tau_cont = (np.arange(K - 1)[:, None] + t[None, :]).reshape(-1)
+    h_cont = (np.linalg.norm(pos - c, axis=2) - total_radius).reshape(-1)
+    tau_disc = np.arange(K)
+    h_disc = np.linalg.norm(X[:pd].T - c.reshape(1, pd), axis=1) - total_radius
+    return tau_cont, h_cont, tau_disc, h_disc
+
+
+def min_inter_agent_separation_continuous(X_list: List[np.ndarray], U_list: List[np.ndarray], foh_or_model, sigma,
+                                          S: int = 8, device="cuda"):
+    """Closest approach of any two agents in continuous time (not in the reference): (d_min_global, d_seg, info).
+
+    X_list / U_list: per agent (n, K) / (m, K); foh_or_model: a FirstOrderHold, a model object or a built-in
+    device model name; sigma: one horizon for all agents or one per agent.  Agents are compared at equal
+    normalised time.  d_seg (N, K-1): per agent and segment the minimum distance to any other agent over the
+    segment; info: j (N, K-1) the other agent, tau (N, K-1) the position in the segment where it occurs,
+    argmin = (i, j, k, tau) of d_min_global.
+
+    Accuracy: exact for the piecewise-linear interpolant of S samples per segment; within max ||r''|| h^2 / 8 of
+    the continuous minimum, h = 1 / ((K-1) S) in normalised time and r the relative position (double integrator:
+    ||r''|| <= 2 max(sigma^2 ||u||))."""
+    import torch
+    if isinstance(foh_or_model, FirstOrderHold):
+        model = builtin_model(foh_or_model.model, "min_inter_agent_separation_continuous")
+        params, device = getattr(foh_or_model.model, "scvx_params", None), getattr(foh_or_model, "_device", device)
+    elif isinstance(foh_or_model, str):
+        model, params = foh_or_model, None
+    else:
+        model = builtin_model(foh_or_model, "min_inter_agent_separation_continuous")
+        params = getattr(foh_or_model, "scvx_params", None)
+    N = len(X_list)
+    if len(U_list) != N:
+        raise ValueError("min_inter_agent_separation_continuous: X_list and U_list must have the same length")
+    sig = np.broadcast_to(np.asarray(sigma, float), (N,)).copy()
+    K = np.asarray(X_list[0]).shape[1]
+    nsub = max(16, scvx_hip.default_nsub(model, float(sig.max()), K)) if model not in ("di", "si") else None
+    out = scvx_hip.fleet_separation(model, _stack(X_list, device), _stack(U_list, device),
+                                    torch.as_tensor(sig, device=device), S=S, nsub=nsub, params=params)
+    info = dict(j=out["j"].cpu().numpy(), tau=out["tau"].cpu().numpy(), argmin=out["argmin"])
+    return out["min"], out["sep"].cpu().numpy(), info

@@ -12,6 +12,10 @@ kernels run on torch's current HIP stream, nothing falls back to the CPU.
     QPSpec                 problem template of qp_solve_batched
     SCPSpec / SCPSolver    the SCvx convex subproblem SCProblem (+ AgentSolver ADMM terms)
                            (SCvx/optimization/sc_problem.py:15-83, agent_solver.py:78-102)
+    fleet_separation       continuous-time closest approach of every agent to every other (rollout_dense +
+                           separation_scan; no reference counterpart)
+    pair_min_distance      node-level pairwise / agent-obstacle minimum distances
+    obstacle_min_distance  (SCvx/utils/analysis.py:10-62)
 """
 import ctypes
 import math
@@ -35,7 +39,8 @@ NSUB_SCALE = {"quad": (5.0 / 49.0, 0.75)}
 QUAD_PARAMS = (1.0, 9.81, 0.02, 0.02, 0.04)
 
 __all__ = ["model_dims", "model_id", "default_nsub", "foh_batched", "jacobi_update", "jacobi_update_global", "integrate_nonlinear", "collision_rows", "collision_check", "qp_solve_batched", "QPSpec", "SCPSpec", "SCPSolver", "slab_update",
-           "intersample_batched",
+           "intersample_batched", "rollout_dense", "separation_scan", "fleet_separation", "pair_min_distance",
+           "obstacle_min_distance",
            "disc_stride", "unpack_disc", "ScvxError", "MODEL_DIMS", "DEFAULT_NSUB"]
 
 
@@ -716,3 +721,129 @@ def intersample_batched(model, X, U, sigma, obstacles, proj=None, dt=1.0, seg_dt
         check(rc, "scvx_intersample_batched")
         del keep
     return {k: v[:, :, :O] for k, v in out.items()}
+
+
+def rollout_dense(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=None, stream=None):
+    """Dense samples of every segment's nonlinear roll-out (scvx_rollout_dense_batched): X (N,K,n), U (N,K,m),
+    sigma (N,) float64 device tensors -> (P, L), P (N,K-1,S+1,3) the first pos_dim states at tau = s/S of each
+    segment (zeros past pos_dim), L (N,K-1) the polyline length of those samples.  Restarts at every node, as
+    integrate_nonlinear(piecewise=True).  RK4 with sub = ceil(nsub / S) steps between samples; nsub None:
+    default_nsub for the batch's longest interval (exact for "di" / "si").  pos_dim None: 2 for the unicycle,
+    else 3.  Built-in models only."""
+    torch = _torch()
+    if not isinstance(model, str):
+        raise NotImplementedError("rollout_dense: compiled for the built-in models only (no runtime-compiled form)")
+    if X.dim() != 3 or U.dim() != 3:
+        raise ValueError("rollout_dense: X (N,K,n) and U (N,K,m) expected")
+    N, K, n = X.shape
+    m = U.shape[2]
+    if (n, m) != MODEL_DIMS[model]:
+        raise ValueError(f"{model}: expected n,m={MODEL_DIMS[model]}, got {(n, m)}")
+    if tuple(U.shape[:2]) != (N, K) or tuple(sigma.shape) != (N,) or K < 2:
+        raise ValueError(f"rollout_dense: U (N,K,m) and sigma (N,) must match X (N,K,n), K >= 2; got "
+                         f"{tuple(U.shape)}, {tuple(sigma.shape)}")
+    pos_dim = (2 if model == "unicycle" else 3) if pos_dim is None else int(pos_dim)
+    S = int(S)
+    if not 1 <= S <= 16 or not 1 <= pos_dim <= min(3, n):
+        raise ValueError(f"rollout_dense: 1 <= S <= 16 and 1 <= pos_dim <= {min(3, n)} required, got S={S}, "
+                         f"pos_dim={pos_dim}")
+    nsub = int(nsub or _auto_nsub(model, sigma, K))
+    if nsub < 1:
+        raise ValueError("rollout_dense: nsub >= 1 required")
+    P = torch.empty((N, K - 1, S + 1, 3), dtype=torch.float64, device=X.device)
+    L = torch.empty((N, K - 1), dtype=torch.float64, device=X.device)
+    keep, pp = _params(model, params)
+    rc = lib().scvx_rollout_dense_batched(MODEL_IDS[model], pp, K, N, _dev(X, name="X"), _dev(U, name="U"),
+                                          _dev(sigma, name="sigma"), S, -(-nsub // S), pos_dim, _dev(P, name="P"),
+                                          _dev(L, name="L"), _stream(stream))
+    check(rc, "scvx_rollout_dense_batched")
+    del keep
+    return P, L
+
+
+def separation_scan(P_all, L_all, i0, n_local, stream=None, prune=True):
+    """Continuous-time closest approach of local agents [i0, i0+n_local) to every other agent of P_all
+    (N_total,K-1,S+1,3) / L_all (N_total,K-1) (rollout_dense's outputs) at equal normalised time
+    (scvx_separation_scan_batched).  Per (local agent, segment), device tensors: sep the minimum chord distance
+    (+inf when there is no other agent), j the other agent and s the sub-interval it occurs in (-1, -1 then),
+    alpha its position in the sub-interval, tau = (s + alpha) / S its position in the segment (nan when j < 0).
+    First minimum in the order j, then s.  Exact for the piecewise-linear interpolant of the samples: within
+    max ||r''|| h^2 / 8 of the continuous minimum, h = 1 / ((K-1) S) in normalised time, r the relative position.
+    prune=False (tests) disables the skip of far neighbours; the outputs are bit-identical."""
+    torch = _torch()
+    if P_all.dim() != 4 or P_all.shape[3] != 3 or P_all.shape[2] < 2 or tuple(L_all.shape) != tuple(P_all.shape[:2]):
+        raise ValueError("separation_scan: P_all (N_total,K-1,S+1,3) and L_all (N_total,K-1) expected")
+    N_total, Km1, S = P_all.shape[0], P_all.shape[1], P_all.shape[2] - 1
+    i0, n_local = int(i0), int(n_local)
+    if S > 16 or Km1 < 1 or i0 < 0 or n_local < 0 or i0 + n_local > N_total:
+        raise ValueError(f"separation_scan: S <= 16, K >= 2 and 0 <= i0, i0 + n_local <= N_total required; got S={S}, "
+                         f"K-1={Km1}, i0={i0}, n_local={n_local}, N_total={N_total}")
+    dev = P_all.device
+    sep = torch.empty((n_local, Km1), dtype=torch.float64, device=dev)
+    arg = torch.empty((n_local, Km1, 2), dtype=torch.int32, device=dev)
+    alpha = torch.empty((n_local, Km1), dtype=torch.float64, device=dev)
+    rc = lib().scvx_separation_scan_batched(Km1 + 1, S, N_total, _dev(P_all, name="P_all"), _dev(L_all, name="L_all"),
+                                            i0, n_local, _dev(sep, name="sep"), _dev(arg, torch.int32, "arg"),
+                                            _dev(alpha, name="alpha"), 0 if prune else 1, _stream(stream))
+    check(rc, "scvx_separation_scan_batched")
+    j, s = arg[..., 0], arg[..., 1]
+    tau = torch.where(j >= 0, (s.to(torch.float64) + alpha) / S, torch.full_like(alpha, float("nan")))
+    return dict(sep=sep, j=j, s=s, alpha=alpha, tau=tau)
+
+
+def fleet_separation(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=None, stream=None):
+    """rollout_dense + separation_scan of a whole fleet: how close any two agents come, between the nodes as
+    well as at them.  Returns separation_scan's dict plus P, L (the samples), agent_min (N,) each agent's
+    minimum over its segments, min (float) the fleet's minimum and argmin = (i, j, k, tau) where it occurs
+    (None for a single agent).  The accuracy statement of separation_scan applies; for the double integrator
+    ||r''|| <= 2 max(sigma^2 ||u||) in normalised time."""
+    P, L = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim, params=params, stream=stream)
+    out = separation_scan(P, L, 0, X.shape[0], stream=stream)
+    out.update(P=P, L=L, agent_min=out["sep"].min(dim=1).values)
+    flat = int(out["sep"].argmin().item())
+    i, k = divmod(flat, X.shape[1] - 1)
+    out["min"] = float(out["sep"][i, k].item())
+    out["argmin"] = (i, int(out["j"][i, k].item()), k, float(out["tau"][i, k].item())) if X.shape[0] > 1 else None
+    return out
+
+
+def pair_min_distance(X, rows=None, stream=None):
+    """min_inter_agent_distance's matrix (SCvx/utils/analysis.py:10-31) on the device: X (N,K,n) -> D (N,N),
+    D[i,j] = min_k ||X[i,k,:rows] - X[j,k,:rows]||, symmetric with a zero diagonal.  rows None: min(3, n), the
+    reference's rows 0:3 of whatever state it is given (scvx_pair_min_distance_batched)."""
+    torch = _torch()
+    if X.dim() != 3 or X.shape[1] < 1:
+        raise ValueError("pair_min_distance: X (N,K,n) expected")
+    N, K, n = X.shape
+    rows = min(3, n) if rows is None else int(rows)
+    if not 1 <= rows <= min(3, n):
+        raise ValueError(f"pair_min_distance: 1 <= rows <= {min(3, n)} required, got {rows}")
+    D = torch.empty((N, N), dtype=torch.float64, device=X.device)
+    rc = lib().scvx_pair_min_distance_batched(K, n, rows, N, _dev(X, name="X"), _dev(D, name="D"), _stream(stream))
+    check(rc, "scvx_pair_min_distance_batched")
+    return D
+
+
+def obstacle_min_distance(X, obstacles, robot_radius, stream=None):
+    """min_agent_obstacle_distance's matrix (SCvx/utils/analysis.py:34-62) on the device: X (N,K,n >= 3),
+    obstacles [(centre (3,), radius)] -> D (N,M), D[i,o] = min_k (||X[i,k,:3] - c_o|| - (robot_radius + r_o))
+    (scvx_obstacle_min_distance_batched)."""
+    import numpy as np
+    torch = _torch()
+    if X.dim() != 3 or X.shape[1] < 1 or X.shape[2] < 3:
+        raise ValueError("obstacle_min_distance: X (N,K,n) with n >= 3 expected")
+    N, K, n = X.shape
+    M = len(obstacles)
+    c = np.array([np.asarray(c, float).reshape(-1) for c, _ in obstacles], float).reshape(M, -1)
+    if M and c.shape[1] != 3:
+        raise ValueError("obstacle_min_distance: obstacle centres must have 3 coordinates")
+    D = torch.empty((N, M), dtype=torch.float64, device=X.device)
+    if M == 0:
+        return D
+    cd = torch.as_tensor(np.ascontiguousarray(c), device=X.device)
+    rd = torch.as_tensor(np.array([float(r) for _, r in obstacles]), device=X.device)
+    rc = lib().scvx_obstacle_min_distance_batched(K, n, N, _dev(X, name="X"), M, _dev(cd, name="centers"),
+                                                  _dev(rd, name="radii"), float(robot_radius), _dev(D, name="D"),
+                                                  _stream(stream))
+    check(rc, "scvx_obstacle_min_distance_batched")
+    return D

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("SCVX_HIP_LIB") or os.path.join(HERE, "libscvx_hip.so"
 
 # the C-ABI revision these bindings are written for (SCVX_HIP_VERSION of include/scvx_hip.h): a library of
 # another revision would take these argument lists with shifted pointers, so lib() refuses it
-SCVX_HIP_VERSION = 6
+SCVX_HIP_VERSION = 7
 SCVX_MAX_BOX, SCVX_MAX_OBS, SCVX_MAX_NBR = 4, 16, 32
 SCVX_IS_MAX_PROJ, SCVX_IS_MAX_STATE = 3, 12
 MODEL_IDS = {"di": 0, "unicycle": 1, "si": 2, "quad": 3}
@@ -27,7 +27,8 @@ EXPORTS = ("scvx_version", "scvx_last_error", "scvx_foh_batched", "scvx_integrat
            "scvx_slab_update_batched", "scvx_jacobi_update_batched", "scvx_rtc_model_create",
            "scvx_rtc_model_source", "scvx_rtc_model_log", "scvx_rtc_model_destroy", "scvx_rtc_foh_batched",
            "scvx_rtc_integrate_nonlinear_batched", "scvx_rtc_subproblem_compile", "scvx_rtc_intersample_batched",
-           "scvx_jacobi_update_costs_batched", "scvx_jacobi_global_rule")
+           "scvx_jacobi_update_costs_batched", "scvx_jacobi_global_rule", "scvx_rollout_dense_batched",
+           "scvx_separation_scan_batched", "scvx_pair_min_distance_batched", "scvx_obstacle_min_distance_batched")
 SCVX_MAX_MODEL_PARAMS, SCVX_RTC_MAX_NX, SCVX_RTC_MAX_NU = 16, 16, 8
 
 
@@ -122,6 +123,10 @@ def lib():
         L.scvx_jacobi_update_batched.argtypes = [i32, i32, i32, i32] + [vp] * 9 + [i32, dbl, dbl, vp]
         L.scvx_jacobi_update_costs_batched.argtypes = [i32, i32, i32, i32] + [vp] * 8 + [vp]
         L.scvx_jacobi_global_rule.argtypes = [i32, i32] + [vp] * 6 + [i32, dbl, vp]
+        L.scvx_rollout_dense_batched.argtypes = [i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+        L.scvx_separation_scan_batched.argtypes = [i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp]
+        L.scvx_pair_min_distance_batched.argtypes = [i32, i32, i32, i32, vp, vp, vp]
+        L.scvx_obstacle_min_distance_batched.argtypes = [i32, i32, i32, vp, i32, vp, vp, dbl, vp, vp]
         cpp = ctypes.POINTER(ctypes.c_char_p)
         L.scvx_rtc_model_create.argtypes = [i32, i32, cpp, cpp, cpp, ctypes.c_char_p, ctypes.POINTER(vp)]
         L.scvx_rtc_model_source.argtypes = [vp]

@@ -15,8 +15,8 @@ import dataclasses
 from dataclasses import dataclass
 from typing import Optional
 
-from . import (QPSolver, QPSpec, collision_check, collision_rows, collision_rows_indexed, default_nsub, foh_batched,
-               jacobi_update, jacobi_update_global, model_dims)
+from . import (QPSolver, QPSpec, collision_check, collision_rows, collision_rows_indexed, default_nsub, fleet_separation,
+               foh_batched, jacobi_update, jacobi_update_global, model_dims)
 
 
 def balanced_order(iters, world):
@@ -224,6 +224,15 @@ class JacobiSCvx:
         work = self.torch.distributed.all_gather_into_tensor(self.X_all, X.contiguous(), group=self.group,
                                                              async_op=async_op)
         return work if async_op else self.X_all
+
+    def separation(self, X, U, S=8):
+        """Continuous-time closest approach of every agent to every other at the iterate (X, U)
+        (scvx_hip.fleet_separation: S samples per segment, the FOH's substep count, the template's pos_dim) --
+        the between-nodes check the node-level collision rows cannot give.  Single rank only."""
+        if self.world > 1:
+            raise NotImplementedError("JacobiSCvx.separation at world > 1 needs the all-gather of the dense samples P "
+                                      "(and L) across ranks before the scan, which is not implemented")
+        return fleet_separation(self.spec.model, X, U, self.sigma, S=S, nsub=self.nsub, pos_dim=self.spec.pos_dim)
 
     def _mark(self, marks, name):
         """Record a timing event named `name` on the current (launch) stream (marks: list or None)."""

@@ -27,7 +27,8 @@
 extern "C" {
 #endif
 
-#define SCVX_HIP_VERSION 6   /* 6: scvx_jacobi_update_costs_batched + scvx_jacobi_global_rule (the global rule fused) */
+#define SCVX_HIP_VERSION 7   /* 7: fleet separation analysis (scvx_rollout_dense_batched, scvx_separation_scan_batched,
+                                  scvx_pair_min_distance_batched, scvx_obstacle_min_distance_batched) */
 
 #define SCVX_OK 0
 #define SCVX_EINVAL (-1)
@@ -468,6 +469,51 @@ int scvx_jacobi_update_costs_batched(int N, int K, int n_x, int n_u, const int32
                                      double* U_out, double* cost, void* stream);
 int scvx_jacobi_global_rule(int N, int mode, const int32_t* status, const double* cost, const double* total_in,
                             double* total_out, double* tr, double* prev_total, int grow, double tr_max, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fleet separation analysis (version 7; csrc/separation.hip): how close any two agents of a finished run
+ * come, at the nodes (SCvx/utils/analysis.py:10-62) and between them (no reference counterpart).
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * Dense samples of every segment's nonlinear roll-out: for agent a and segment k < K-1 the roll-out from
+ * X[a][k] under the FOH input u_k + tau/dt (u_{k+1} - u_k), dt = sigma[a]/(K-1) (the piecewise semantics of
+ * scvx_integrate_nonlinear_batched: restart at every node), sampled at tau_s = s/S dt, s = 0..S.  Fixed-step
+ * RK4 with `sub` steps between consecutive samples (exact for the double and the single integrator).
+ *   X [N][K][n], U [N][K][m], sigma [N]  ->  P [N][K-1][S+1][3]  the first pos_dim states, zeros past pos_dim
+ *                                            L [N][K-1]          polyline length of those samples
+ * Limits: 1 <= S <= 16, 1 <= pos_dim <= 3.  Built-in models only: SCVX_MODEL_RUNTIME returns
+ * SCVX_EUNSUPPORTED.  params as scvx_foh_batched.
+ */
+int scvx_rollout_dense_batched(int model_id, const double* params, int K, int N, const double* X, const double* U,
+                               const double* sigma, int S, int sub, int pos_dim, double* P, double* L, void* stream);
+
+/*
+ * Continuous-time closest approach on those samples.  For local agents [i0, i0 + N_local) of P_all
+ * [N_total][K-1][S+1][3] / L_all [N_total][K-1] (all-gathered, as X_all of scvx_collision_rows_batched) and
+ * every segment k: the minimum over j != i and sub-intervals s < S, at equal normalised time, of the chord
+ * closest approach
+ *     d0 = p_i(s) - p_j(s), d1 = p_i(s+1) - p_j(s+1), e = d1 - d0,
+ *     a = 0 if e.e == 0 else clamp(-d0.e / e.e, 0, 1),   dist = ||d0 + a e||.
+ * Outputs: sep [N_local][K-1], arg [N_local][K-1][2] int32 = (j, s), alpha [N_local][K-1] = a.  The scan runs
+ * j ascending, then s ascending, and a candidate replaces the kept one only when strictly smaller: the first
+ * minimum.  N_total == 1: sep = +inf, arg = (-1, -1).  Exact for the piecewise-linear interpolant of the
+ * samples; within max ||r''|| h^2 / 8 of the continuous minimum (r the relative position, h the sub-interval).
+ * flags: 0; bit 0 (tests only) disables the skip of neighbours whose |d(s=0)| - (L_i + L_j) cannot be
+ * strictly smaller than the kept minimum -- the outputs are bit-identical either way.
+ */
+int scvx_separation_scan_batched(int K, int S, int N_total, const double* P_all, const double* L_all, int i0,
+                                 int N_local, double* sep, int32_t* arg, double* alpha, int flags, void* stream);
+
+/* min_inter_agent_distance (SCvx/utils/analysis.py:10-31): D [N][N] = min_k ||X_i[0:rows, k] - X_j[0:rows, k]||
+ * over the K nodes of X [N][K][n_x]; symmetric, zero diagonal.  rows <= 3 (the reference takes rows 0:3 of
+ * whatever state it is given, the unicycle's heading included). */
+int scvx_pair_min_distance_batched(int K, int n_x, int rows, int N, const double* X, double* D, void* stream);
+
+/* min_agent_obstacle_distance (analysis.py:34-62): D [N][n_obs] = min_k (||X_i[0:3, k] - c_o|| - (robot_radius +
+ * r_o)); centers [n_obs][3], radii [n_obs] (device).  n_x >= 3. */
+int scvx_obstacle_min_distance_batched(int K, int n_x, int N, const double* X, int n_obs, const double* centers,
+                                       const double* radii, double robot_radius, double* D, void* stream);
 
 #ifdef __cplusplus
 }

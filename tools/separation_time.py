@@ -1,0 +1,69 @@
+"""Times the fleet separation analysis (csrc/separation.hip) on the GPU: rollout_dense, separation_scan (with
+and without the chunk skip, alternating) and pair_min_distance at the C3 shape (1024 double integrators,
+K = 50, S = 8; bench.make_workload's trajectories) and the C4 shape (4096 agents on the 16^3 lattice;
+workloads.synthetic_lattice).  HIP events around each launch, median of 20 launches after 5 warm-ups.
+Prints one JSON line per (shape, kernel) with the algorithmic chord-test count N^2 (K-1) S x 25 FLOP and the
+fraction of the 78.6 TFLOP/s FP64 vector peak that count corresponds to (the skip does less than the count, so
+its figure is an equivalent rate, not an achieved one).
+usage: python tools/separation_time.py [S]"""
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "dynamic-programming-multiagent-trajectory-optimiziation_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+import scvx_hip  # noqa: E402
+from scvx_hip import workloads  # noqa: E402
+
+WARMUP, REPS = 5, 20
+PEAK_FP64 = 78.6e12
+CHORD_FLOP = 25
+
+
+def timed(fns):
+    """Median milliseconds of each callable: WARMUP rounds, then REPS rounds, the callables alternating."""
+    ms = {k: [] for k in fns}
+    for r in range(WARMUP + REPS):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if r >= WARMUP:
+                ms[k].append(e0.elapsed_time(e1))
+    return {k: float(np.median(v)) for k, v in ms.items()}
+
+
+def main(S=8):
+    S = int(S)
+    dev = torch.device("cuda:0")
+    shapes = {"c3": workloads.synthetic_di(1024, K=bench.K, seed=1, sigma=bench.SIGMA, obstacles=bench.N_OBS),
+              "c4": workloads.synthetic_lattice(side=16, K=bench.K, seed=2, sigma=bench.SIGMA)}
+    for name, sc in shapes.items():
+        X, U, sig = (torch.tensor(sc[k], device=dev) for k in ("X", "U", "sigma"))
+        N, K = X.shape[0], X.shape[1]
+        P, L = scvx_hip.rollout_dense("di", X, U, sig, S=S)
+        a, b = scvx_hip.separation_scan(P, L, 0, N), scvx_hip.separation_scan(P, L, 0, N, prune=False)
+        same = all(torch.equal(a[k], b[k]) for k in ("sep", "j", "s", "alpha"))
+        t = timed({"rollout_dense": lambda: scvx_hip.rollout_dense("di", X, U, sig, S=S),
+                   "separation_scan": lambda: scvx_hip.separation_scan(P, L, 0, N),
+                   "separation_scan_unpruned": lambda: scvx_hip.separation_scan(P, L, 0, N, prune=False),
+                   "pair_min_distance": lambda: scvx_hip.pair_min_distance(X)})
+        flop = float(N) * N * (K - 1) * S * CHORD_FLOP
+        for k, ms in t.items():
+            rec = dict(shape=name, N=N, K=K, S=S, kernel=k, median_ms=round(ms, 4))
+            if k.startswith("separation_scan"):
+                rec.update(algorithmic_gflop=round(flop / 1e9, 2), fp64_peak_fraction=round(flop / (ms * 1e-3) / PEAK_FP64, 4))
+            print(json.dumps(rec), flush=True)
+        print(json.dumps(dict(shape=name, min_separation=float(a["sep"].min().item()),
+                              pruned_equals_unpruned=bool(same))), flush=True)
+
+
+if __name__ == "__main__":
+    main(*sys.argv[1:2])
