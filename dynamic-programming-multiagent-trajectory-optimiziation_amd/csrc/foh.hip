@@ -1,6 +1,7 @@
 // Batched First-Order-Hold discretization and nonlinear roll-outs of the built-in models
 // (MI355X / gfx950, float64).  The integrator bodies (algorithm, lane mapping, roofline) live in
-// csrc/foh_body.hpp, shared with the runtime-compiled user models of csrc/foh_rtc.hip.
+// csrc/foh_body.hpp, shared with the runtime-compiled user models of csrc/foh_rtc.hip; the model id is
+// resolved by csrc/models.hpp (dispatch_model, model_params).
 #include <hip/hip_runtime.h>
 
 #include "models.hpp"
@@ -51,15 +52,6 @@ static int launch_nl(const double* X, const double* U, const double* sigma, doub
     return check_launch("nonlinear_kernel");
 }
 
-static ModelParams make_params(int model_id, const double* params) {
-    ModelParams P{};
-    if (model_id == Quadrotor12::ID) {
-        const double dflt[5] = {1.0, 9.81, 0.02, 0.02, 0.04};
-        for (int i = 0; i < 5; ++i) P.p[i] = params ? params[i] : dflt[i];
-    }
-    return P;
-}
-
 }  // namespace scvx
 
 using namespace scvx;
@@ -68,15 +60,10 @@ extern "C" int scvx_foh_batched(int model_id, const double* params, int K, int N
                                 const double* sigma, int nsub, double* out, void* stream) {
     if (K < 2 || N < 0 || nsub < 1 || !X || !U || !sigma || !out) return set_error(SCVX_EINVAL, "foh: bad args");
     if (N == 0) return SCVX_OK;
-    const ModelParams P = make_params(model_id, params);
-    hipStream_t st = (hipStream_t)stream;
-    switch (model_id) {
-        case DoubleIntegrator3D::ID: return launch_foh<DoubleIntegrator3D>(X, U, sigma, out, K, N, nsub, P, st);
-        case Unicycle::ID: return launch_foh<Unicycle>(X, U, sigma, out, K, N, nsub, P, st);
-        case SingleIntegrator3D::ID: return launch_foh<SingleIntegrator3D>(X, U, sigma, out, K, N, nsub, P, st);
-        case Quadrotor12::ID: return launch_foh<Quadrotor12>(X, U, sigma, out, K, N, nsub, P, st);
-        default: return set_error(SCVX_EUNSUPPORTED, "foh: unknown model id");
-    }
+    const ModelParams P = model_params(model_id, params);
+    return dispatch_model(model_id, "foh", [&](auto tag) {
+        return launch_foh<typename decltype(tag)::type>(X, U, sigma, out, K, N, nsub, P, (hipStream_t)stream);
+    });
 }
 
 extern "C" int scvx_integrate_nonlinear_batched(int model_id, const double* params, int K, int N, const double* X,
@@ -84,13 +71,8 @@ extern "C" int scvx_integrate_nonlinear_batched(int model_id, const double* para
                                                 double* Xout, void* stream) {
     if (K < 2 || N < 0 || nsub < 1 || !X || !U || !sigma || !Xout) return set_error(SCVX_EINVAL, "nl: bad args");
     if (N == 0) return SCVX_OK;
-    const ModelParams P = make_params(model_id, params);
-    hipStream_t st = (hipStream_t)stream;
-    switch (model_id) {
-        case DoubleIntegrator3D::ID: return launch_nl<DoubleIntegrator3D>(X, U, sigma, Xout, K, N, nsub, piecewise, P, st);
-        case Unicycle::ID: return launch_nl<Unicycle>(X, U, sigma, Xout, K, N, nsub, piecewise, P, st);
-        case SingleIntegrator3D::ID: return launch_nl<SingleIntegrator3D>(X, U, sigma, Xout, K, N, nsub, piecewise, P, st);
-        case Quadrotor12::ID: return launch_nl<Quadrotor12>(X, U, sigma, Xout, K, N, nsub, piecewise, P, st);
-        default: return set_error(SCVX_EUNSUPPORTED, "nl: unknown model id");
-    }
+    const ModelParams P = model_params(model_id, params);
+    return dispatch_model(model_id, "nl", [&](auto tag) {
+        return launch_nl<typename decltype(tag)::type>(X, U, sigma, Xout, K, N, nsub, piecewise, P, (hipStream_t)stream);
+    });
 }

@@ -1,9 +1,10 @@
-// FOH and nonlinear roll-out kernel bodies, templated on the model (gfx950, float64).
+// FOH and nonlinear roll-out kernel bodies and the roll-outs' one RK4 state step (rk4_step), templated on the model
+// (gfx950, float64).
 //
 // Shared by the built-in models (csrc/foh.hip: compiled with the library) and by runtime-compiled
 // user models (csrc/foh_rtc.hip: this file is embedded in the library as text and handed to hipRTC
-// as a header, so both paths run the same integrator).  Self-contained: no other header of the
-// library is visible to hipRTC.
+// as a header, so both paths run the same integrator).  Self-contained: it includes no other
+// header of the library.
 //
 // A model is a struct with
 //   static constexpr int N, M;                                   state / input dimension
@@ -153,6 +154,34 @@ __device__ __forceinline__ void foh_body(const double* __restrict__ X, const dou
     }
 }
 
+// One classical RK4 step of x' = f(x, u0 + (t/T) du) from time t, step h, in place: the state step of every nonlinear
+// roll-out -- nonlinear_body below, rollout_dense_kernel (separation.hip), the h() of intersample_body.hpp.  The
+// caller owns its expressions for t and h; T is the length of the interval the input is interpolated over.
+template <class Mdl>
+__device__ __forceinline__ void rk4_step(double* x, double t, double h, double T, const double* u0, const double* du,
+                                         const ModelParams& P) {
+    constexpr int n = Mdl::N, m = Mdl::M;
+    auto fx = [&](double ts, const double* xs, double* o) {
+        double u[m];
+#pragma unroll
+        for (int j = 0; j < m; ++j) u[j] = u0[j] + (ts / T) * du[j];
+        Mdl::f(xs, u, o, P);
+    };
+    double k_[n], acc[n], xt[n];
+    fx(t, x, k_);
+#pragma unroll
+    for (int i = 0; i < n; ++i) { acc[i] = k_[i]; xt[i] = x[i] + 0.5 * h * k_[i]; }
+    fx(t + 0.5 * h, xt, k_);
+#pragma unroll
+    for (int i = 0; i < n; ++i) { acc[i] += 2.0 * k_[i]; xt[i] = x[i] + 0.5 * h * k_[i]; }
+    fx(t + 0.5 * h, xt, k_);
+#pragma unroll
+    for (int i = 0; i < n; ++i) { acc[i] += 2.0 * k_[i]; xt[i] = x[i] + h * k_[i]; }
+    fx(t + h, xt, k_);
+#pragma unroll
+    for (int i = 0; i < n; ++i) x[i] += h / 6.0 * (acc[i] + k_[i]);
+}
+
 // integrate_nonlinear_piecewise (first_order_hold.py:127-140): one lane per (agent, interval),
 // restart from X[:,k] each interval, physical time [0, dt*sigma], u interpolated by t/(dt*sigma).
 // integrate_nonlinear_full (:142-155): one lane per agent, chained over the intervals.
@@ -180,28 +209,7 @@ __device__ __forceinline__ void nonlinear_body(const double* __restrict__ X, con
         double u0[m], du[m];
 #pragma unroll
         for (int j = 0; j < m; ++j) { u0[j] = u0p[j]; du[j] = u0p[m + j] - u0[j]; }
-        auto fx = [&](double t, const double* xs, double* o) {
-            double u[m];
-#pragma unroll
-            for (int j = 0; j < m; ++j) u[j] = u0[j] + (t / T) * du[j];
-            Mdl::f(xs, u, o, P);
-        };
-        for (int sstep = 0; sstep < nsub; ++sstep) {
-            const double t = sstep * h;
-            double k_[n], acc[n], xt[n];
-            fx(t, x, k_);
-#pragma unroll
-            for (int i = 0; i < n; ++i) { acc[i] = k_[i]; xt[i] = x[i] + 0.5 * h * k_[i]; }
-            fx(t + 0.5 * h, xt, k_);
-#pragma unroll
-            for (int i = 0; i < n; ++i) { acc[i] += 2.0 * k_[i]; xt[i] = x[i] + 0.5 * h * k_[i]; }
-            fx(t + 0.5 * h, xt, k_);
-#pragma unroll
-            for (int i = 0; i < n; ++i) { acc[i] += 2.0 * k_[i]; xt[i] = x[i] + h * k_[i]; }
-            fx(t + h, xt, k_);
-#pragma unroll
-            for (int i = 0; i < n; ++i) x[i] += h / 6.0 * (acc[i] + k_[i]);
-        }
+        for (int sstep = 0; sstep < nsub; ++sstep) rk4_step<Mdl>(x, sstep * h, h, T, u0, du, P);
 #pragma unroll
         for (int i = 0; i < n; ++i) Xout[(agent * K + k + 1) * n + i] = x[i];
     }

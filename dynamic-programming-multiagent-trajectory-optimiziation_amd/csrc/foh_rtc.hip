@@ -4,21 +4,16 @@
 // (SCvx/discretization/first_order_hold.py:13-50, 89-125).  The built-in models of csrc/models.hpp
 // are compiled into the library; a user model arrives as C expressions (include/scvx_hip.h), is
 // wrapped into a model struct with the csrc/models.hpp contract and compiled by hipRTC together with
-// csrc/foh_body.hpp -- the integrator the built-in models use, embedded here as text at build time --
+// csrc/foh_body.hpp -- the integrator the built-in models use, embedded in the library as text at build time --
 // into two extern "C" kernels.  The Jacobians are applied as sparse matrix-vector products: entries
 // given as structural zeros generate no code.
 //
 // Compile at create (host only, no GPU needed); load the code object per device at the first
-// launch (hipModuleLoadData).  Launch through hipModuleLaunchKernel on the caller's stream.
+// launch; launch on the caller's stream -- all through the library's hipRTC layer (csrc/rtc_common.hpp).  This
+// file keeps what is the user model's own: generate(), the scvx_rtc_model handle and its entry points.
 #include <hip/hip_runtime.h>
-#ifndef SCVX_OFFLOAD_ARCH
-#define SCVX_OFFLOAD_ARCH "gfx950"
-#endif
-#include <hip/hiprtc.h>
 
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -26,21 +21,10 @@
 #include "common.hpp"
 #include "foh_body.hpp"  // ModelParams (the launch argument)
 #include "intersample_body.hpp"  // ISArgs, intersample_check
+#include "rtc_common.hpp"
 #include "scvx_hip.h"
 
 namespace {
-
-// csrc/foh_body.hpp, csrc/intersample_body.hpp and include/scvx_hip.h as string literals (build/*.inc, generated
-// by the Makefile)
-const char* const kFohBody =
-#include "foh_body.hpp.inc"
-    ;
-const char* const kIsBody =
-#include "intersample_body.hpp.inc"
-    ;
-const char* const kScvxHdrF =
-#include "scvx_hip.h.inc"
-    ;
 
 bool is_zero(const char* e) {
     if (!e) return true;
@@ -113,49 +97,16 @@ std::string generate(int n, int m, const char* const* f, const char* const* A, c
     return s;
 }
 
-struct Loaded {
-    hipModule_t mod = nullptr;
-    hipFunction_t foh = nullptr, nl = nullptr, is = nullptr;
-};
-
 }  // namespace
 
 struct scvx_rtc_model {
     int n = 0, m = 0;
     std::string src, log;
     std::vector<char> code;
-    std::mutex mu;
-    std::map<int, Loaded> loaded;  // device -> module
+    mutable scvx::rtc::Modules mods;  // per device, loaded at the first launch there
 };
 
 namespace {
-
-int load(const scvx_rtc_model* cm, Loaded* out) {
-    auto* md = const_cast<scvx_rtc_model*>(cm);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return scvx::set_error(SCVX_ELAUNCH, "rtc: no HIP device");
-    std::lock_guard<std::mutex> g(md->mu);
-    auto it = md->loaded.find(dev);
-    if (it != md->loaded.end()) { *out = it->second; return SCVX_OK; }
-    Loaded L;
-    hipError_t e = hipModuleLoadData(&L.mod, md->code.data());
-    if (e != hipSuccess) {
-        std::string msg = std::string("rtc: hipModuleLoadData: ") + hipGetErrorString(e);
-        return scvx::set_error(SCVX_ELAUNCH, msg.c_str());
-    }
-    if (hipModuleGetFunction(&L.foh, L.mod, "scvx_rtc_foh") != hipSuccess ||
-        hipModuleGetFunction(&L.nl, L.mod, "scvx_rtc_nonlinear") != hipSuccess) {
-        (void)hipModuleUnload(L.mod);
-        return scvx::set_error(SCVX_ELAUNCH, "rtc: kernels missing from the code object");
-    }
-    if (md->n <= SCVX_IS_MAX_STATE && hipModuleGetFunction(&L.is, L.mod, "scvx_rtc_intersample") != hipSuccess) {
-        (void)hipModuleUnload(L.mod);
-        return scvx::set_error(SCVX_ELAUNCH, "rtc: intersample kernel missing from the code object");
-    }
-    md->loaded[dev] = L;
-    *out = L;
-    return SCVX_OK;
-}
 
 int params_of(const double* params, int n_params, scvx::ModelParams* P) {
     if (n_params < 0 || n_params > SCVX_MAX_MODEL_PARAMS || (n_params > 0 && !params))
@@ -163,6 +114,14 @@ int params_of(const double* params, int n_params, scvx::ModelParams* P) {
     std::memset(P, 0, sizeof(*P));
     for (int i = 0; i < n_params; ++i) P->p[i] = params[i];
     return SCVX_OK;
+}
+
+// kernel `name` of the model on the current device, over `total` lanes in blocks of `block`
+int launch(const scvx_rtc_model* md, const char* what, const char* name, long long total, int block, void** args,
+           void* stream) {
+    hipFunction_t f = nullptr;
+    if (int rc = md->mods.function("rtc", md->code, name, &f)) return rc;
+    return scvx::rtc::launch(what, f, (unsigned)((total + block - 1) / block), block, 0, (hipStream_t)stream, args);
 }
 
 }  // namespace
@@ -178,40 +137,8 @@ extern "C" int scvx_rtc_model_create(int n_x, int n_u, const char* const* f_expr
     md->n = n_x;
     md->m = n_u;
     md->src = generate(n_x, n_u, f_exprs, A_exprs, B_exprs, prelude);
-    hiprtcProgram prog;
-    const char* hdr_src[3] = {kFohBody, kIsBody, kScvxHdrF};
-    const char* hdr_name[3] = {"foh_body.hpp", "intersample_body.hpp", "scvx_hip.h"};
-    if (hiprtcCreateProgram(&prog, md->src.c_str(), "scvx_user_model.hip", 3, hdr_src, hdr_name) !=
-        HIPRTC_SUCCESS) {
-        delete md;
-        return scvx::set_error(SCVX_EINVAL, "rtc: hiprtcCreateProgram failed");
-    }
-    // the library's own target (the Makefile's ARCH): a user model's code object loads where the library runs
-    const char* opts[] = {"--offload-arch=" SCVX_OFFLOAD_ARCH, "-O3", "-std=c++17"};
-    const hiprtcResult rc = hiprtcCompileProgram(prog, 3, opts);
-    size_t ls = 0;
-    if (hiprtcGetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-        md->log.resize(ls);
-        hiprtcGetProgramLog(prog, &md->log[0]);
-        md->log.resize(std::strlen(md->log.c_str()));
-    }
-    if (rc != HIPRTC_SUCCESS) {
-        hiprtcDestroyProgram(&prog);
-        std::string msg = std::string("rtc: compile failed: ") + hiprtcGetErrorString(rc) + "\n" + md->log;
-        *out = md;  // kept so that the caller can read the log and the source; destroy it
-        return scvx::set_error(SCVX_EINVAL, msg.c_str());
-    }
-    size_t cs = 0;
-    hiprtcGetCodeSize(prog, &cs);
-    md->code.resize(cs);
-    hiprtcGetCode(prog, md->code.data());
-    hiprtcDestroyProgram(&prog);
-    if (cs == 0) {
-        *out = md;
-        return scvx::set_error(SCVX_EINVAL, "rtc: empty code object");
-    }
-    *out = md;
-    return SCVX_OK;
+    *out = md;  // also when the compile fails, so that the caller can read the log and the source; destroy it
+    return scvx::rtc::compile("rtc", md->src, "scvx_user_model.hip", nullptr, &md->code, &md->log);
 }
 
 extern "C" const char* scvx_rtc_model_source(const scvx_rtc_model* model) { return model ? model->src.c_str() : ""; }
@@ -219,13 +146,7 @@ extern "C" const char* scvx_rtc_model_log(const scvx_rtc_model* model) { return 
 
 extern "C" int scvx_rtc_model_destroy(scvx_rtc_model* model) {
     if (!model) return SCVX_OK;
-    for (auto& kv : model->loaded) {
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        (void)hipSetDevice(kv.first);
-        (void)hipModuleUnload(kv.second.mod);
-        (void)hipSetDevice(cur);
-    }
+    model->mods.unload_all();
     delete model;
     return SCVX_OK;
 }
@@ -238,17 +159,9 @@ extern "C" int scvx_rtc_foh_batched(const scvx_rtc_model* model, const double* p
     scvx::ModelParams P;
     if (int rc = params_of(params, n_params, &P)) return rc;
     if (N == 0) return SCVX_OK;
-    Loaded L;
-    if (int rc = load(model, &L)) return rc;
     const long long total = (long long)N * (K - 1) * (model->n + 2 * model->m + 2);
-    const unsigned grid = (unsigned)((total + 255) / 256);
     void* args[] = {(void*)&X, (void*)&U, (void*)&sigma, (void*)&out, (void*)&K, (void*)&N, (void*)&nsub, (void*)&P};
-    hipError_t e = hipModuleLaunchKernel(L.foh, grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-    if (e != hipSuccess) {
-        std::string msg = std::string("rtc foh launch: ") + hipGetErrorString(e);
-        return scvx::set_error(SCVX_ELAUNCH, msg.c_str());
-    }
-    return SCVX_OK;
+    return launch(model, "rtc foh", "scvx_rtc_foh", total, 256, args, stream);
 }
 
 extern "C" int scvx_rtc_integrate_nonlinear_batched(const scvx_rtc_model* model, const double* params, int n_params,
@@ -260,19 +173,10 @@ extern "C" int scvx_rtc_integrate_nonlinear_batched(const scvx_rtc_model* model,
     scvx::ModelParams P;
     if (int rc = params_of(params, n_params, &P)) return rc;
     if (N == 0) return SCVX_OK;
-    Loaded L;
-    if (int rc = load(model, &L)) return rc;
     const long long total = piecewise ? (long long)N * (K - 1) : (long long)N;
-    const int block = piecewise ? 256 : 64;
-    const unsigned grid = (unsigned)((total + block - 1) / block);
     void* args[] = {(void*)&X, (void*)&U, (void*)&sigma, (void*)&Xout, (void*)&K, (void*)&N, (void*)&nsub,
                     (void*)&piecewise, (void*)&P};
-    hipError_t e = hipModuleLaunchKernel(L.nl, grid, 1, 1, block, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-    if (e != hipSuccess) {
-        std::string msg = std::string("rtc nl launch: ") + hipGetErrorString(e);
-        return scvx::set_error(SCVX_ELAUNCH, msg.c_str());
-    }
-    return SCVX_OK;
+    return launch(model, "rtc nl", "scvx_rtc_nonlinear", total, piecewise ? 256 : 64, args, stream);
 }
 
 extern "C" int scvx_rtc_intersample_batched(const scvx_rtc_model* model, const double* params, int n_params,
@@ -286,21 +190,13 @@ extern "C" int scvx_rtc_intersample_batched(const scvx_rtc_model* model, const d
     if (N == 0 || tpl->n_obs == 0) return SCVX_OK;
     if (!X || !U || !sigma || !n_crit || !t_crit || !h0 || !grad_x || !grad_u)
         return scvx::set_error(SCVX_EINVAL, "rtc intersample: null buffer");
-    Loaded L;
-    if (int rc = load(model, &L)) return rc;
     scvx::ISArgs a{};
     a.T = *tpl;
     a.K = K; a.N = N;
     a.X = X; a.U = U; a.sigma = sigma;
     a.n_crit = n_crit; a.t_crit = t_crit; a.h0 = h0; a.grad_x = grad_x; a.grad_u = grad_u;
     a.P = P;
-    const long long nwork = (long long)N * (K - 1) * tpl->n_obs;
-    const unsigned grid = (unsigned)((nwork + 255) / 256);
     void* args[] = {(void*)&a};
-    hipError_t e = hipModuleLaunchKernel(L.is, grid, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr);
-    if (e != hipSuccess) {
-        std::string msg = std::string("rtc intersample launch: ") + hipGetErrorString(e);
-        return scvx::set_error(SCVX_ELAUNCH, msg.c_str());
-    }
-    return SCVX_OK;
+    return launch(model, "rtc intersample", "scvx_rtc_intersample", (long long)N * (K - 1) * tpl->n_obs, 256, args,
+                  stream);
 }

@@ -46,12 +46,7 @@ extern "C" int scvx_intersample_batched(const scvx_intersample_template* tpl, co
     a.X = X; a.U = U; a.sigma = sigma;
     a.n_crit = n_crit; a.t_crit = t_crit; a.h0 = h0; a.grad_x = grad_x; a.grad_u = grad_u;
     a.P = model_params(T.model_id, params);
-    hipStream_t st = (hipStream_t)stream;
-    switch (T.model_id) {
-        case DoubleIntegrator3D::ID: return launch_is<DoubleIntegrator3D>(a, st);
-        case Unicycle::ID: return launch_is<Unicycle>(a, st);
-        case SingleIntegrator3D::ID: return launch_is<SingleIntegrator3D>(a, st);
-        case Quadrotor12::ID: return launch_is<Quadrotor12>(a, st);
-        default: return set_error(SCVX_EUNSUPPORTED, "intersample: unknown model id");
-    }
+    return dispatch_model(T.model_id, "intersample", [&](auto tag) {
+        return launch_is<typename decltype(tag)::type>(a, (hipStream_t)stream);
+    });
 }

@@ -19,7 +19,7 @@
 //                                  roll-out ignores its u argument, so grad_u is identically 0, as in
 //                                  the reference).
 // The reference integrates with LSODA (odeint, rtol = atol = 1.49e-8); here each roll-out is fixed-step
-// RK4 with nsub steps (exact for the single integrator, whose x(t) is quadratic).
+// RK4 with nsub steps (rk4_step of foh_body.hpp; exact for the single integrator, whose x(t) is quadratic).
 //
 // Mapping: one lane per (agent, k, obstacle); everything a lane needs (x_k, u_k, u_{k+1}, T, the
 // obstacle) sits in registers, each roll-out restarts from x_k (the reference's semantics: odeint
@@ -32,7 +32,7 @@
 #include <cmath>
 #endif
 
-#include "foh_body.hpp"   // ModelParams
+#include "foh_body.hpp"   // ModelParams, rk4_step
 #include "scvx_hip.h"     // scvx_intersample_template
 
 namespace scvx {
@@ -81,29 +81,7 @@ __device__ __forceinline__ void intersample_body(const ISArgs& a) {
 #pragma unroll
         for (int i = 0; i < n; ++i) x[i] = x0[i];
         const double hs = t * dtp / nsub;
-        auto fx = [&](double tau, const double* xs, double* out) {
-            double u[m];
-            const double w = tau / dtp;
-#pragma unroll
-            for (int j = 0; j < m; ++j) u[j] = u0[j] + w * du[j];
-            Mdl::f(xs, u, out, a.P);
-        };
-        for (int s = 0; s < nsub; ++s) {
-            const double tau = s * hs;
-            double kk[n], acc[n], xt[n];
-            fx(tau, x, kk);
-#pragma unroll
-            for (int i = 0; i < n; ++i) { acc[i] = kk[i]; xt[i] = x[i] + 0.5 * hs * kk[i]; }
-            fx(tau + 0.5 * hs, xt, kk);
-#pragma unroll
-            for (int i = 0; i < n; ++i) { acc[i] += 2.0 * kk[i]; xt[i] = x[i] + 0.5 * hs * kk[i]; }
-            fx(tau + 0.5 * hs, xt, kk);
-#pragma unroll
-            for (int i = 0; i < n; ++i) { acc[i] += 2.0 * kk[i]; xt[i] = x[i] + hs * kk[i]; }
-            fx(tau + hs, xt, kk);
-#pragma unroll
-            for (int i = 0; i < n; ++i) x[i] += (hs / 6.0) * (acc[i] + kk[i]);
-        }
+        for (int s = 0; s < nsub; ++s) rk4_step<Mdl>(x, s * hs, hs, dtp, u0, du, a.P);
         double d2 = 0.0;
         for (int i = 0; i < pd; ++i) {
             double p = -c[i];

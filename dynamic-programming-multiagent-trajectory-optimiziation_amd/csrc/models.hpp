@@ -9,9 +9,14 @@
 //   Unicycle            x=[x,y,th], u=[v,w]   SCvx/models/unicycle_model.py:54-63
 //   SingleIntegrator3D  f=u                   SCvx/models/single_integrator_model.py:54-57
 //   Quadrotor12         build-defined 6-DoF rigid body
+// Host side (end of the file): model_params, a model id's parameter block, and dispatch_model, the one switch from
+// a model id to its type that every launcher of a model-templated kernel goes through.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string>
+
+#include "common.hpp"    // set_error
 #include "foh_body.hpp"  // ModelParams
 
 namespace scvx {
@@ -176,6 +181,23 @@ inline ModelParams model_params(int model_id, const double* params) {
         for (int i = 0; i < 5; ++i) P.p[i] = params ? params[i] : dflt[i];
     }
     return P;
+}
+
+// host-side: the one switch over the built-in models.  Calls fn(ModelTag<Mdl>{}) for the model of `model_id` and
+// returns its result; an unknown id is SCVX_EUNSUPPORTED "<who>: unknown model id"
+template <class Mdl>
+struct ModelTag {
+    using type = Mdl;
+};
+template <class Fn>
+inline int dispatch_model(int model_id, const char* who, Fn&& fn) {
+    switch (model_id) {
+        case DoubleIntegrator3D::ID: return fn(ModelTag<DoubleIntegrator3D>{});
+        case Unicycle::ID: return fn(ModelTag<Unicycle>{});
+        case SingleIntegrator3D::ID: return fn(ModelTag<SingleIntegrator3D>{});
+        case Quadrotor12::ID: return fn(ModelTag<Quadrotor12>{});
+        default: return set_error(SCVX_EUNSUPPORTED, (std::string(who) + ": unknown model id").c_str());
+    }
 }
 
 }  // namespace scvx

@@ -44,7 +44,7 @@ constexpr int SEP_CH = 4;   // neighbours per branch-free chunk
 constexpr double SEP_SKIP_MARGIN = 1e-12;
 
 // one lane per (agent, segment): restart at X[:,k], FOH input u_k + tau/T (u_{k+1} - u_k), T = sigma/(K-1)
-// (nonlinear_body's piecewise roll-out, foh_body.hpp), sampled every `sub` RK4 steps
+// (nonlinear_body's piecewise roll-out, foh_body.hpp), sampled every `sub` RK4 steps (rk4_step)
 template <class Mdl>
 __global__ __launch_bounds__(64) void rollout_dense_kernel(const double* __restrict__ X, const double* __restrict__ U,
                                                            const double* __restrict__ sigma, double* __restrict__ P,
@@ -63,12 +63,6 @@ __global__ __launch_bounds__(64) void rollout_dense_kernel(const double* __restr
     const double* u0p = U + (agent * K + k) * m;
 #pragma unroll
     for (int j = 0; j < m; ++j) { u0[j] = u0p[j]; du[j] = u0p[m + j] - u0[j]; }
-    auto fx = [&](double t, const double* xs, double* o) {
-        double u[m];
-#pragma unroll
-        for (int j = 0; j < m; ++j) u[j] = u0[j] + (t / T) * du[j];
-        Mdl::f(xs, u, o, Pm);
-    };
     double* out = P + tid * (long long)(S + 1) * 3;
     double prev[3], len = 0.0;
 #pragma unroll
@@ -77,22 +71,7 @@ __global__ __launch_bounds__(64) void rollout_dense_kernel(const double* __restr
         out[d] = prev[d];
     }
     for (int s = 1; s <= S; ++s) {
-        for (int i = 0; i < sub; ++i) {
-            const double t = ((long long)(s - 1) * sub + i) * h;
-            double k_[n], acc[n], xt[n];
-            fx(t, x, k_);
-#pragma unroll
-            for (int q = 0; q < n; ++q) { acc[q] = k_[q]; xt[q] = x[q] + 0.5 * h * k_[q]; }
-            fx(t + 0.5 * h, xt, k_);
-#pragma unroll
-            for (int q = 0; q < n; ++q) { acc[q] += 2.0 * k_[q]; xt[q] = x[q] + 0.5 * h * k_[q]; }
-            fx(t + 0.5 * h, xt, k_);
-#pragma unroll
-            for (int q = 0; q < n; ++q) { acc[q] += 2.0 * k_[q]; xt[q] = x[q] + h * k_[q]; }
-            fx(t + h, xt, k_);
-#pragma unroll
-            for (int q = 0; q < n; ++q) x[q] += h / 6.0 * (acc[q] + k_[q]);
-        }
+        for (int i = 0; i < sub; ++i) rk4_step<Mdl>(x, ((long long)(s - 1) * sub + i) * h, h, T, u0, du, Pm);
         double l2 = 0.0;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
@@ -310,16 +289,10 @@ extern "C" int scvx_rollout_dense_batched(int model_id, const double* params, in
     if (model_id == SCVX_MODEL_RUNTIME)
         return set_error(SCVX_EUNSUPPORTED, "rollout_dense: built-in models only (no runtime-compiled form)");
     const ModelParams Pm = model_params(model_id, params);
-    hipStream_t st = (hipStream_t)stream;
-#define SCVX_ROLL(M) launch_rollout_dense<M>(X, U, sigma, P, L, K, N, S, sub, pos_dim, Pm, st)
-    switch (model_id) {
-        case DoubleIntegrator3D::ID: return SCVX_ROLL(DoubleIntegrator3D);
-        case Unicycle::ID: return SCVX_ROLL(Unicycle);
-        case SingleIntegrator3D::ID: return SCVX_ROLL(SingleIntegrator3D);
-        case Quadrotor12::ID: return SCVX_ROLL(Quadrotor12);
-        default: return set_error(SCVX_EUNSUPPORTED, "rollout_dense: unknown model id");
-    }
-#undef SCVX_ROLL
+    return dispatch_model(model_id, "rollout_dense", [&](auto tag) {
+        return launch_rollout_dense<typename decltype(tag)::type>(X, U, sigma, P, L, K, N, S, sub, pos_dim, Pm,
+                                                                  (hipStream_t)stream);
+    });
 }
 
 extern "C" int scvx_separation_scan_batched(int K, int S, int N_total, const double* P_all, const double* L_all, int i0,

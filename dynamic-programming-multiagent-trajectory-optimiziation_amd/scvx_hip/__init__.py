@@ -131,17 +131,34 @@ def _params(model, params):
     return buf, ctypes.cast(buf, ctypes.c_void_p)
 
 
+def _check_xus(who, model, X, U, sigma):
+    """The (X, U, sigma) batch of a model (built-in name or DeviceModel) as every model-templated kernel indexes it:
+    X (N,K,n), U (N,K,m), sigma (N,).  Returns (N, K, n, m)."""
+    n, m = model_dims(model)
+    shp = tuple(X.shape)
+    if len(shp) != 3 or shp[2] != n or tuple(U.shape) != (shp[0], shp[1], m) or tuple(sigma.shape) != (shp[0],):
+        raise ValueError(f"{who}: X (N,K,{n}), U (N,K,{m}) and sigma (N,) expected; got {shp}, {tuple(U.shape)}, "
+                         f"{tuple(sigma.shape)}")
+    return shp[0], shp[1], n, m
+
+
+def _fill_obstacles(t, obstacles, rows=None):
+    """n_obs, obs_center, obs_radius of a template (QP, SCP, inter-sample; the caller has checked the count) from
+    [(centre, radius)].  rows: the length every centre must have."""
+    t.n_obs = len(obstacles)
+    for o, (c, r) in enumerate(obstacles):
+        if rows is not None and len(c) != rows:
+            raise ValueError("obstacle centres must match the projection rows")
+        for i in range(len(c)):
+            t.obs_center[o][i] = float(c[i])
+        t.obs_radius[o] = float(r)
+
+
 def foh_batched(model, X, U, sigma, nsub=None, params=None, out=None, stream=None):
     """X (N,K,n), U (N,K,m), sigma (N,) float64 device tensors -> disc (N,K-1,n(n+2m+2)).  nsub None: default_nsub
     for the batch's longest interval (for the quadrotor this reads max(sigma) on the host; pass nsub to avoid it)."""
     torch = _torch()
-    N, K, n = X.shape
-    m = U.shape[2]
-    if (n, m) != MODEL_DIMS[model]:
-        raise ValueError(f"{model}: expected n,m={MODEL_DIMS[model]}, got {(n, m)}")
-    if tuple(U.shape[:2]) != (N, K) or tuple(sigma.shape) != (N,):
-        raise ValueError(f"foh_batched: U (N,K,m) and sigma (N,) must match X (N,K,n); got "
-                         f"{tuple(U.shape)}, {tuple(sigma.shape)}")
+    N, K, n, m = _check_xus("foh_batched", model, X, U, sigma)
     if out is None:
         out = torch.empty((N, K - 1, disc_stride(model)), dtype=torch.float64, device=X.device)
     keep, pp = _params(model, params)
@@ -155,13 +172,7 @@ def foh_batched(model, X, U, sigma, nsub=None, params=None, out=None, stream=Non
 def integrate_nonlinear(model, X, U, sigma, piecewise, nsub=16, params=None, out=None, stream=None):
     """Batched FirstOrderHold.integrate_nonlinear_piecewise (piecewise=True) / _full (False)."""
     torch = _torch()
-    N, K, n = X.shape
-    m = U.shape[2] if U.dim() == 3 else -1
-    if (n, m) != MODEL_DIMS[model]:
-        raise ValueError(f"{model}: expected n,m={MODEL_DIMS[model]}, got {(n, m)}")
-    if tuple(U.shape[:2]) != (N, K) or tuple(sigma.shape) != (N,):
-        raise ValueError(f"integrate_nonlinear: U (N,K,m) and sigma (N,) must match X (N,K,n); got "
-                         f"{tuple(U.shape)}, {tuple(sigma.shape)}")
+    N, K, n, m = _check_xus("integrate_nonlinear", model, X, U, sigma)
     if out is None:
         out = torch.empty_like(X)
     keep, pp = _params(model, params)
@@ -273,11 +284,7 @@ class QPSpec:
         t.n_box = len(self.box)
         for i, (bi, lo, hi) in enumerate(self.box):
             t.box_idx[i], t.box_lo[i], t.box_hi[i] = int(bi), float(lo), float(hi)
-        t.n_obs = len(self.obs)
-        for o, (c, r) in enumerate(self.obs):
-            for i in range(len(c)):
-                t.obs_center[o][i] = float(c[i])
-            t.obs_radius[o] = float(r)
+        _fill_obstacles(t, self.obs)
         t.w_obs, t.j_max, t.w_coll = float(self.w_obs), int(self.j_max), float(self.w_coll)
         t.has_soc = int(self.u_max is not None)
         t.u_max = 0.0 if self.u_max is None else float(self.u_max)
@@ -447,11 +454,7 @@ class SCPSpec:
         t.n_xbound = len(self.x_bounds)
         for b, (i, lo, hi) in enumerate(self.x_bounds):
             t.xb_idx[b], t.xb_lo[b], t.xb_hi[b] = int(i), float(lo), float(hi)
-        t.n_obs = len(self.obs)
-        for o, (c, r) in enumerate(self.obs):
-            for i in range(len(c)):
-                t.obs_center[o][i] = float(c[i])
-            t.obs_radius[o] = float(r)
+        _fill_obstacles(t, self.obs)
         t.w_nu, t.w_slack, t.w_sigma = float(self.w_nu), float(self.w_slack), float(self.w_sigma)
         t.n_nbr, t.rho, t.d_min, t.w_coll = int(self.n_nbr), float(self.rho), float(self.d_min), float(self.w_coll)
         t.max_iter, t.tol, t.reg = int(self.max_iter), float(self.tol), float(self.reg)
@@ -494,23 +497,28 @@ class SCPSolver:
         self.iters = torch.empty(N, dtype=torch.int32, device=device)
         self._dummy = torch.zeros(1, dtype=f64, device=device)
 
+    def _call(self, entry, inputs, optional, outputs, stream):
+        """Marshal one solve for the C entry point `entry`: the template and N, the seven inputs solve() and
+        solve_game() share, the entry point's three optional tensors as (name, tensor or None) (None: the dummy
+        buffer), its output buffers, the workspace and the stream."""
+        names = ("disc", "Xref", "Uref", "sigma_ref", "tr", "x_init", "x_final")
+        args = [_dev(t, name=k) for k, t in zip(names, inputs)]
+        args += [_dev(self._dummy if t is None else t, name=k) for k, t in optional]
+        args += [_dev(t, t.dtype) for t in outputs]
+        rc = getattr(lib(), entry)(ctypes.byref(self.ctpl), self.N, *args, _dev(self.workspace),
+                                   ctypes.c_size_t(self.workspace.numel() * 8), _stream(stream))
+        check(rc, entry)
+
     def solve(self, disc, Xref, Uref, sigma_ref, tr, x_init, x_final, nbr_pos=None, nbr_Y=None, nbr_Lam=None,
               stream=None):
         """disc (N,K-1,n(n+2m+2)), Xref (N,K,n), Uref (N,K,m), sigma_ref (N,), tr (N,), x_init/x_final (N,n);
         nbr_* (N,n_nbr,K,pos_dim) when spec.n_nbr > 0.  Returns dict of device tensors (reused buffers)."""
         if self.spec.n_nbr > 0 and (nbr_pos is None or nbr_Y is None or nbr_Lam is None):
             raise ValueError("ADMM terms need nbr_pos, nbr_Y and nbr_Lam")
-        d = self._dummy
-        rc = lib().scvx_scp_solve_batched(
-            ctypes.byref(self.ctpl), self.N, _dev(disc, name="disc"), _dev(Xref, name="Xref"), _dev(Uref, name="Uref"),
-            _dev(sigma_ref, name="sigma_ref"), _dev(tr, name="tr"), _dev(x_init, name="x_init"),
-            _dev(x_final, name="x_final"), _dev(nbr_pos if nbr_pos is not None else d, name="nbr_pos"),
-            _dev(nbr_Y if nbr_Y is not None else d, name="nbr_Y"),
-            _dev(nbr_Lam if nbr_Lam is not None else d, name="nbr_Lam"), _dev(self.X), _dev(self.U), _dev(self.nu),
-            _dev(self.sigma), _dev(self.s_obs), _dev(self.s_nbr), _dev(self.obj), _dev(self.status, _torch().int32),
-            _dev(self.iters, _torch().int32), _dev(self.workspace), ctypes.c_size_t(self.workspace.numel() * 8),
-            _stream(stream))
-        check(rc, "scvx_scp_solve_batched")
+        self._call("scvx_scp_solve_batched", (disc, Xref, Uref, sigma_ref, tr, x_init, x_final),
+                   (("nbr_pos", nbr_pos), ("nbr_Y", nbr_Y), ("nbr_Lam", nbr_Lam)),
+                   (self.X, self.U, self.nu, self.sigma, self.s_obs, self.s_nbr, self.obj, self.status, self.iters),
+                   stream)
         return dict(X=self.X, U=self.U, nu=self.nu, sigma=self.sigma, s_obs=self.s_obs[:, :len(self.spec.obs)],
                     s_nbr=self.s_nbr[:, :self.spec.n_nbr], obj=self.obj, status=self.status, iters=self.iters)
 
@@ -529,17 +537,9 @@ class SCPSolver:
             shp = (N, sp_.n_slab, K, pd)
             if slab_z is None or slab_P is None or tuple(slab_z.shape) != shp or tuple(slab_P.shape) != shp:
                 raise ValueError(f"slab_z / slab_P {shp} required")
-        d = self._dummy
-        rc = lib().scvx_scp_game_solve_batched(
-            ctypes.byref(self.ctpl), N, _dev(disc, name="disc"), _dev(Xref, name="Xref"), _dev(Uref, name="Uref"),
-            _dev(sigma_ref, name="sigma_ref"), _dev(tr, name="tr"), _dev(x_init, name="x_init"),
-            _dev(x_final, name="x_final"), _dev(X_prev if X_prev is not None else d, name="X_prev"),
-            _dev(slab_z if slab_z is not None else d, name="slab_z"),
-            _dev(slab_P if slab_P is not None else d, name="slab_P"), _dev(self.X), _dev(self.U), _dev(self.nu),
-            _dev(self.sigma), _dev(self.s_obs), _dev(self.obj), _dev(self.status, _torch().int32),
-            _dev(self.iters, _torch().int32), _dev(self.workspace), ctypes.c_size_t(self.workspace.numel() * 8),
-            _stream(stream))
-        check(rc, "scvx_scp_game_solve_batched")
+        self._call("scvx_scp_game_solve_batched", (disc, Xref, Uref, sigma_ref, tr, x_init, x_final),
+                   (("X_prev", X_prev), ("slab_z", slab_z), ("slab_P", slab_P)),
+                   (self.X, self.U, self.nu, self.sigma, self.s_obs, self.obj, self.status, self.iters), stream)
         return dict(X=self.X, U=self.U, nu=self.nu, sigma=self.sigma, s_obs=self.s_obs[:, :len(sp_.obs)],
                     obj=self.obj, status=self.status, iters=self.iters)
 
@@ -671,10 +671,7 @@ def intersample_batched(model, X, U, sigma, obstacles, proj=None, dt=1.0, seg_dt
     import numpy as np
     torch = _torch()
     rt = not isinstance(model, str)
-    n, m = model.dims if rt else MODEL_DIMS[model]
-    N, K = X.shape[0], X.shape[1]
-    if X.shape != (N, K, n) or U.shape != (N, K, m) or sigma.shape != (N,):
-        raise ValueError(f"intersample_batched: X (N,K,{n}), U (N,K,{m}), sigma (N,) expected")
+    N, K, n, m = _check_xus("intersample_batched", model, X, U, sigma)
     O = len(obstacles)
     if O > _lib.SCVX_MAX_OBS:
         raise ValueError("too many obstacles")
@@ -683,14 +680,8 @@ def intersample_batched(model, X, U, sigma, obstacles, proj=None, dt=1.0, seg_dt
     pd = len(np.asarray(obstacles[0][0]).reshape(-1)) if O else 1
     Tm = np.eye(n)[:pd] if proj is None else np.asarray(proj, float).reshape(pd, n)
     t = _lib.IntersampleTemplate()
-    t.model_id, t.n_obs, t.proj_rows = (_lib.SCVX_MODEL_RUNTIME if rt else MODEL_IDS[model]), O, pd
-    for o, (c, r) in enumerate(obstacles):
-        c = np.asarray(c, float).reshape(-1)
-        if c.size != pd:
-            raise ValueError("obstacle centres must match the projection rows")
-        for i in range(pd):
-            t.obs_center[o][i] = float(c[i])
-        t.obs_radius[o] = float(r)
+    t.model_id, t.proj_rows = model_id(model), pd
+    _fill_obstacles(t, [(np.asarray(c, float).reshape(-1), r) for c, r in obstacles], rows=pd)
     for i in range(pd):
         for j in range(n):
             t.proj[i * _lib.SCVX_IS_MAX_STATE + j] = float(Tm[i, j])
@@ -733,15 +724,9 @@ def rollout_dense(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=None,
     torch = _torch()
     if not isinstance(model, str):
         raise NotImplementedError("rollout_dense: compiled for the built-in models only (no runtime-compiled form)")
-    if X.dim() != 3 or U.dim() != 3:
-        raise ValueError("rollout_dense: X (N,K,n) and U (N,K,m) expected")
-    N, K, n = X.shape
-    m = U.shape[2]
-    if (n, m) != MODEL_DIMS[model]:
-        raise ValueError(f"{model}: expected n,m={MODEL_DIMS[model]}, got {(n, m)}")
-    if tuple(U.shape[:2]) != (N, K) or tuple(sigma.shape) != (N,) or K < 2:
-        raise ValueError(f"rollout_dense: U (N,K,m) and sigma (N,) must match X (N,K,n), K >= 2; got "
-                         f"{tuple(U.shape)}, {tuple(sigma.shape)}")
+    N, K, n, m = _check_xus("rollout_dense", model, X, U, sigma)
+    if K < 2:
+        raise ValueError("rollout_dense: K >= 2 required")
     pos_dim = (2 if model == "unicycle" else 3) if pos_dim is None else int(pos_dim)
     S = int(S)
     if not 1 <= S <= 16 or not 1 <= pos_dim <= min(3, n):

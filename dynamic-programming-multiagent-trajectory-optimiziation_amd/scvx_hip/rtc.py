@@ -163,13 +163,9 @@ class DeviceModel:
     def foh(self, X, U, sigma, nsub=None, params=None, out=None, stream=None):
         """Batched FirstOrderHold.calculate_discretization: X (N,K,n), U (N,K,m), sigma (N,) float64
         device tensors -> disc (N, K-1, n(n+2m+2)) (layout of scvx_hip.foh_batched)."""
-        from . import _dev, _stream, _torch
+        from . import _check_xus, _dev, _stream, _torch
         torch = _torch()
-        N, K, n = X.shape
-        m = U.shape[2]
-        if (n, m) != self.dims or tuple(U.shape[:2]) != (N, K) or tuple(sigma.shape) != (N,):
-            raise ValueError(f"DeviceModel.foh: X (N,K,{self.n_x}), U (N,K,{self.n_u}), sigma (N,) expected; got "
-                             f"{tuple(X.shape)}, {tuple(U.shape)}, {tuple(sigma.shape)}")
+        N, K, n, m = _check_xus("DeviceModel.foh", self, X, U, sigma)
         if out is None:
             out = torch.empty((N, K - 1, n * (n + 2 * m + 2)), dtype=torch.float64, device=X.device)
         pa, npar = self._pp(params)
@@ -181,11 +177,9 @@ class DeviceModel:
 
     def integrate_nonlinear(self, X, U, sigma, piecewise, nsub=16, params=None, out=None, stream=None):
         """Batched integrate_nonlinear_piecewise (piecewise=True) / integrate_nonlinear_full (False)."""
-        from . import _dev, _stream, _torch
+        from . import _check_xus, _dev, _stream, _torch
         torch = _torch()
-        N, K, n = X.shape
-        if (n, U.shape[2]) != self.dims or tuple(U.shape[:2]) != (N, K) or tuple(sigma.shape) != (N,):
-            raise ValueError("DeviceModel.integrate_nonlinear: shapes do not match the model")
+        N, K, n, _ = _check_xus("DeviceModel.integrate_nonlinear", self, X, U, sigma)
         if out is None:
             out = torch.empty((N, K, n), dtype=torch.float64, device=X.device)
         pa, npar = self._pp(params)
@@ -197,9 +191,8 @@ class DeviceModel:
 
     def unpack_disc(self, disc):
         """[..., K-1, n(n+2m+2)] -> (A_bar, B_bar, C_bar, S_bar, z_bar), as scvx_hip.unpack_disc."""
-        n, m = self.dims
-        o = [0, n * n, n * n + n * m, n * n + 2 * n * m, n * n + 2 * n * m + n, n * n + 2 * n * m + 2 * n]
-        return tuple(disc[..., o[i]:o[i + 1]].transpose(-1, -2) for i in range(5))
+        from . import unpack_disc
+        return unpack_disc(disc, self)
 
 
 # ---- symbolic re-tracing of numpy callables -------------------------------------------------------
