@@ -88,6 +88,13 @@ __device__ __forceinline__ double qp_mask(int a, int b) {
     asm("" : "+v"(m));
     return (double)m;
 }
+// a + b that is never contracted with a product feeding it.  fma(1.0, c, g) rounds c before the sum; written c + g,
+// the backend would fuse a c = x * y into fma(x, y, g) and round once (floating-point contraction is on for the
+// rest of the kernel), so the compile-time form of a masked accumulation goes through this.
+__device__ __forceinline__ double qp_add_nc(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
 // a / b for the per-row barrier quantities (l / s, the rows' Newton terms): the hardware reciprocal, two Newton
 // steps and a product (~1.5 ulp, six instructions) instead of the correctly rounded division sequence (eleven,
 // with a longer dependent chain); these run once per row per phase on every node

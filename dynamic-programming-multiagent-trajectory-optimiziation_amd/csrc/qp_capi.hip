@@ -17,9 +17,15 @@ int qp_launch_di(int idx, const QPArgs& a, hipStream_t st);
 int qp_launch_unicycle(int idx, const QPArgs& a, hipStream_t st);
 int qp_launch_si(int idx, const QPArgs& a, hipStream_t st);
 int qp_launch_quad(int idx, const QPArgs& a, hipStream_t st);
+int qp_select_di(int idx, const scvx_qp_template& T, bool tracing);
 // SCVX_QP_GENERIC_K (qp_inst.hpp): the runtime-K instantiation also where a K-specialised one exists
 bool qp_force_generic_k() {
     const char* e = std::getenv("SCVX_QP_GENERIC_K");
+    return e && e[0] && !(e[0] == '0' && !e[1]);
+}
+// SCVX_QP_GENERIC_FLAGS (qp_inst.hpp): the runtime-flag instantiation also where a flag-specialised one matches
+bool qp_force_generic_flags() {
+    const char* e = std::getenv("SCVX_QP_GENERIC_FLAGS");
     return e && e[0] && !(e[0] == '0' && !e[1]);
 }
 }  // namespace scvx
@@ -40,15 +46,16 @@ struct ModelTable {
     const int* caps;
     int ncaps;
     int (*launch)(int, const QPArgs&, hipStream_t);
+    int (*select)(int, const scvx_qp_template&, bool);   // nullptr: the model has runtime-K instantiations only
 };
 
 // model table entry for the template (nullptr: unknown model / dimensions)
 const ModelTable* model_of(const scvx_qp_template& T) {
     static const ModelTable tab[] = {
-        {6, 3, kCapsDI, (int)(sizeof(kCapsDI) / sizeof(int) / QP_CAPS_W), qp_launch_di},
-        {3, 2, kCapsUni, (int)(sizeof(kCapsUni) / sizeof(int) / QP_CAPS_W), qp_launch_unicycle},
-        {3, 3, kCapsSI, (int)(sizeof(kCapsSI) / sizeof(int) / QP_CAPS_W), qp_launch_si},
-        {12, 4, kCapsQuad, (int)(sizeof(kCapsQuad) / sizeof(int) / QP_CAPS_W), qp_launch_quad},
+        {6, 3, kCapsDI, (int)(sizeof(kCapsDI) / sizeof(int) / QP_CAPS_W), qp_launch_di, qp_select_di},
+        {3, 2, kCapsUni, (int)(sizeof(kCapsUni) / sizeof(int) / QP_CAPS_W), qp_launch_unicycle, nullptr},
+        {3, 3, kCapsSI, (int)(sizeof(kCapsSI) / sizeof(int) / QP_CAPS_W), qp_launch_si, nullptr},
+        {12, 4, kCapsQuad, (int)(sizeof(kCapsQuad) / sizeof(int) / QP_CAPS_W), qp_launch_quad, nullptr},
     };
     const int ids[] = {SCVX_MODEL_DOUBLE_INTEGRATOR, SCVX_MODEL_UNICYCLE, SCVX_MODEL_SINGLE_INTEGRATOR, SCVX_MODEL_QUADROTOR};
     for (int i = 0; i < 4; ++i)
@@ -112,6 +119,18 @@ size_t ws_bytes(const QPClass& c, int N, int K) {
 extern "C" int scvx_qp_set_trace(double* buf, int agent, int cap) {
     g_trace = buf; g_trace_agent = agent; g_trace_cap = buf ? cap : 0;
     return SCVX_OK;
+}
+
+// Diagnostics query (host only, no launch): which instantiation of its class a solve of `tpl` runs right now -- the
+// environment overrides and a trace set by scvx_qp_set_trace included.  0: K and the problem flags at run time;
+// 1: K at compile time; 2: K and the flags at compile time (csrc/qp_inst.hpp qp_select, the function the launch
+// itself calls).  Negative: the template's error code.
+extern "C" int scvx_qp_instantiation(const scvx_qp_template* tpl) {
+    QPClass c;
+    const int rc = qp_check(tpl, 1, c);
+    if (rc != SCVX_OK) return rc < 0 ? rc : -rc;
+    if (c.rt || !c.mt->select) return 0;
+    return c.mt->select(c.cls, *tpl, g_trace != nullptr);
 }
 
 extern "C" size_t scvx_qp_workspace_bytes(const scvx_qp_template* tpl, int N) {

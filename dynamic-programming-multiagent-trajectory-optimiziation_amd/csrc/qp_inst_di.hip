@@ -27,5 +27,9 @@ static_assert(QPCfg<12, 4, 4, 8, 8, 1>::L.FBS == 1182 && QPCfg<12, 4, 4, 8, 8, 1
 int qp_launch_di(int idx, const QPArgs& a, hipStream_t st) {
     return QPDispatch<6, 3, 0, SCVX_CAPS_DI>::launch(idx, a, st);
 }
+// the instantiation qp_launch_di takes for class idx (QP_INST_*), without launching
+int qp_select_di(int idx, const scvx_qp_template& T, bool tracing) {
+    return QPDispatch<6, 3, 0, SCVX_CAPS_DI>::select(idx, T, tracing);
+}
 
 }  // namespace scvx

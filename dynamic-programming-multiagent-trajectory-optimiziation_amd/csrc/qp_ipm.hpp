@@ -57,11 +57,44 @@ struct QPCfg {
     static_assert(qp_class_error(NX_, NU_, NB_, NO_, NC_, VC_, 2, QP_LDS_DEVICE) == nullptr, "class outside the kernel's limits");
 };
 
+// The template's problem flags and row counts, at run time (QPFlagsRT: read from scvx_qp_template, the default) or at
+// compile time (QPFlags<...>: the third axis of qp_ipm_kernel, DESIGN §3.3 "Non-arithmetic instructions").  A
+// QPFlags instantiation states has_final, fix_last_input, ineq_last, has_soc, j_max > 0, n_obs, n_box and box_idx[];
+// it also implies no soft terminal (w_final = 0), no proximal term (w_prox = 0) and no virtual control.  Every row
+// switch (row_on / grp_on), the box rows' state pick and the terminal / proximal / fixed-input selects then fold.
+// The values that stay run-time data (weights, bounds, obstacle geometry, u_max, tol, max_iter) are read from the
+// template as before.  The host launches it only for a template that matches field for field
+// (qp_inst.hpp qp_flags_match).
+struct QPFlagsRT {
+    static constexpr bool spec = false;
+    static constexpr int has_final = 0, fix_last_input = 0, ineq_last = 0, has_soc = 0, has_coll = 0, n_obs = 0, n_box = 0;
+    static constexpr int box_idx(int) { return 0; }
+};
+template <int FIN, int FIXU, int INEQL, int SOC, int COLL, int NOBS, int NBOX, int B0 = 0, int B1 = 0>
+struct QPFlags {
+    static_assert(NBOX >= 0 && NBOX <= 2, "box indices are listed as B0, B1");
+    static constexpr bool spec = true;
+    static constexpr int has_final = FIN, fix_last_input = FIXU, ineq_last = INEQL, has_soc = SOC, has_coll = COLL,
+                         n_obs = NOBS, n_box = NBOX;
+    static constexpr int box_idx(int b) { return b == 0 ? B0 : B1; }
+};
+// the flag-specialised instantiations carry no diagnostics (region timers, the per-iteration trace): the host takes
+// the runtime-flag instantiation while a trace buffer is set.  -DQP_SPEC_TRACE=1 keeps them (tools/build_variant.sh)
+#ifndef QP_SPEC_TRACE
+#define QP_SPEC_TRACE 0
+#endif
+// levers of DESIGN §3.3 "Non-arithmetic instructions", for builds of one lever alone (tools/build_variant.sh):
+// 1 = compile-time flags (host selection), 2 = no diagnostics in the flag-specialised kernel
+#ifndef QP_INSN_STEPS
+#define QP_INSN_STEPS 3
+#endif
+
 // KC: the node count K at compile time (0: T.K at run time).  With KC set, every workspace offset (the column stride,
 // the packet and factor-block bases), the LDS offsets of the K-sized blocks and the chunk geometry are constants;
 // the workspace layout and the arithmetic are those of the KC = 0 instantiation of the same class (a warm start
 // written by one is valid for the other).  The host picks KC = T.K where it is compiled (qp_inst.hpp QPKSpec).
-template <class C, int KC = 0>
+// F: the problem flags (QPFlagsRT or a QPFlags<...>, above).
+template <class C, int KC = 0, class F = QPFlagsRT>
 __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     constexpr int NX = C::L.NX, NU = C::L.NU, NZ = C::L.NZ, NQ = C::L.NQ, NR = C::L.NR, NG = C::L.NG, NS = C::L.NS,
                   NO = C::L.NO, NC = C::L.NC, NB = C::L.NB, PKT = C::L.PKT, NV = C::L.NV, NVA = C::L.NVA;
@@ -80,11 +113,16 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         agent = (o >= 0 && o < a.N) ? o : (long long)blockIdx.x;
     }
     const bool act = t < K;
-    const bool ineq = act && ((t < K - 1) || T.ineq_last);
-    const bool fin = T.has_final != 0;
-    const bool soc = ineq && T.has_soc;
-    const bool has_coll = NC > 0 && T.j_max > 0;
-    const int nobs = T.n_obs, nbox = T.n_box;
+    // the problem flags: constants in a flag-specialised instantiation (F::spec), where everything below folds
+    constexpr bool FS = F::spec;
+    constexpr bool TRACE = !FS || QP_SPEC_TRACE || !(QP_INSN_STEPS & 2);   // diagnostics compiled in
+    double* const trace = TRACE ? a.trace : nullptr;
+    const bool ineq = act && ((t < K - 1) || (FS ? F::ineq_last != 0 : T.ineq_last != 0));
+    const bool fin = FS ? F::has_final != 0 : T.has_final != 0;
+    const bool soc = ineq && (FS ? F::has_soc != 0 : T.has_soc != 0);
+    const bool has_coll = NC > 0 && (FS ? F::has_coll != 0 : T.j_max > 0);
+    const int nobs = FS ? F::n_obs : T.n_obs, nbox = FS ? F::n_box : T.n_box;
+    const bool fix_last = FS ? F::fix_last_input != 0 : T.fix_last_input != 0;
     const int ccount = (ineq && has_coll) ? min((int)a.coll_count[agent * K + t], min(T.j_max, NC)) : 0;
     const double trv = a.tr[agent];
     const double sig = a.sigma[agent];
@@ -97,7 +135,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     if (has_coll) qnorm = fmax(qnorm, T.w_coll);
     // soft terminal state (has_final = 0, w_final > 0): + w_final ||x_{K-1} - x_final||^2, linear term
     // -2 w_final x_final at node K-1 (a build-side option for nonlinear models, no reference row)
-    const bool soft_fin = !fin && T.w_final > 0.0;
+    const bool soft_fin = !FS && !fin && T.w_final > 0.0;
     if (soft_fin) {
         for (int i = 0; i < NX; ++i) qnorm = fmax(qnorm, 2.0 * T.w_final * fabs(a.x_final[agent * NX + i]));
     }
@@ -106,7 +144,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     const bool vact = NV > 0 && act && t < K - 1;
     const bool warm = a.warm != nullptr && a.warm[agent] != 0;   // wave-uniform
     // proximal term w_prox ||x_t - xbar_t||^2 (every node): linear term -2 w_prox xbar_t
-    const bool prox = T.w_prox > 0.0;
+    const bool prox = !FS && T.w_prox > 0.0;
     if (prox) {
         double qp = 0.0;
         for (int i = 0; i < NX; ++i) qp = fmax(qp, act ? 2.0 * T.w_prox * fabs(a.Xref[(agent * K + (act ? t : 0)) * NX + i]) : 0.0);
@@ -126,7 +164,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         cpx = wave_sum(v);
     }
     const double wu = ((t < K - 1) ? 1.0 : T.w_last) * iosc;
-    const bool fixed_u = act && (t == K - 1) && T.fix_last_input;
+    const bool fixed_u = act && (t == K - 1) && fix_last;
     const bool tsoft = soft_fin && act && (t == K - 1);
     const double wfs = tsoft ? T.w_final * iosc : 0.0;
     const double* disc = a.disc + agent * (long long)(K - 1) * C::L.DSTR;
@@ -230,7 +268,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         return r;
     };
     // region timers of the traced agent (diagnostics): cycles since the previous stamp -> V_ST[i]
-    const bool stamp_on = a.trace && agent == a.trace_agent;
+    const bool stamp_on = trace && agent == a.trace_agent;
     long long tprev = 0;
     auto stamp = [&](int i) __attribute__((always_inline)) {
         if (stamp_on) {
@@ -242,7 +280,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             // the region's workspace bytes (every lane's) -> trace buffer after the cycle slots (host: 8 cap + 36)
             const double b = wave_sum(wb.nby);
             wb.nby = 0.0;
-            if (lane == 0 && i >= 0) a.trace[8 * a.trace_cap + 20 + i] += b;
+            if (lane == 0 && i >= 0) trace[8 * a.trace_cap + 20 + i] += b;
 #endif
         }
     };
@@ -661,7 +699,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             pstamp(12);
             // ---- phase 3: Rh = L D L' in registers (every lane); [K | kappa] = -Rh^-1 [Sh | W2]
             {
-                const bool fx = last && T.fix_last_input;
+                const bool fx = last && fix_last;
                 // the phase body is compiled twice for the stiff-facet classes: CAND for a candidate node (the facet
                 // branch, the stage system) and the plain body for every other stage (the straight-line code of the
                 // classes without facets), one scalar branch between them
@@ -1828,7 +1866,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
         for (int q = 0; q < (SGS ? 0 : NS); ++q) { hold(sg[q], 3); hold(&sb[q], 1); }
 #pragma unroll
-        for (int b = 0; b < NB; ++b) bidx[b] = qp_opaque(T.box_idx[b]);
+        for (int b = 0; b < NB; ++b) bidx[b] = FS ? F::box_idx(b) : qp_opaque(T.box_idx[b]);
     };
     auto load_state = [&]() __attribute__((always_inline)) {
         fresh();
@@ -1860,11 +1898,28 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         if (r < C::L.R_GRP) return (r - C::L.R_COL) < ccount;
         return grp_on(r - C::L.R_GRP);
     };
-    auto sel_x = [&](const double* zz, int idx) __attribute__((always_inline)) -> double {
-        double v = 0.0;
+    // g + m c with m = 1.0 where state component i is box b's, else 0.0: fma(m, c, g) with an opaque mask for a
+    // runtime index (qp_mask).  With the index a compile-time constant the masks are literals: fma(1.0, c, g) is
+    // c + g rounded once (qp_add_nc: c, often a product, must stay rounded on its own as the fma's operand was), and
+    // fma(0.0, c, g) stays an FMA -- it is not g for g = -0.0 or a non-finite c, and the compiler may not assume
+    // otherwise.  Every component sees the runtime-flag instantiation's operation, without the compare / select /
+    // convert per mask.
+    auto bacc = [&](int i, int b, double c, double g) __attribute__((always_inline)) -> double {
+        if constexpr (FS) return i == F::box_idx(b) ? qp_add_nc(c, g) : fma(0.0, c, g);
+        else return fma(qp_mask(i, bidx[b]), c, g);
+    };
+    // component box_idx[b] of zz.  The masked pick is the chain v = fma(m_i, zz[i], v) from v = +0.0: for finite zz
+    // it is zz[idx] + 0.0 (the terms before idx leave +0.0, fma(1, zz[idx], +0.0) turns -0.0 into +0.0, the terms
+    // after add a zero to it), which is what the direct pick computes; the add does not fold, for the same reason.
+    auto sel_x = [&](const double* zz, int b) __attribute__((always_inline)) -> double {
+        if constexpr (FS) {
+            return zz[F::box_idx(b)] + 0.0;
+        } else {
+            double v = 0.0;
 #pragma unroll
-        for (int i = 0; i < NX; ++i) v = fma(qp_mask(i, idx), zz[i], v);
-        return v;
+            for (int i = 0; i < NX; ++i) v = fma(qp_mask(i, bidx[b]), zz[i], v);
+            return v;
+        }
     };
     // G_r [z; a] and h_r of row r (static after unrolling)
     auto row_eval = [&](int r, const double* zz, const double* aa, double& gz, double& h) __attribute__((always_inline)) {
@@ -1878,7 +1933,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             }
         } else if (r < C::L.R_OBS) {
             const int b = (r - C::L.R_BOX) >> 1, lo = (r - C::L.R_BOX) & 1;
-            const double xi = sel_x(zz, bidx[b]);
+            const double xi = sel_x(zz, b);
             gz = lo ? -xi : xi; h = lo ? -T.box_lo[b] : T.box_hi[b];
         } else if (r < C::L.R_GRP) {
             const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
@@ -1894,9 +1949,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
             for (int j = 0; j < NU; ++j) gzv[NX + j] += ((r >> j) & 1) ? -c : c;
         } else if (r < C::L.R_OBS) {
-            const int b = (r - C::L.R_BOX) >> 1, lo = (r - C::L.R_BOX) & 1, idx = bidx[b];
+            const int b = (r - C::L.R_BOX) >> 1, lo = (r - C::L.R_BOX) & 1;
 #pragma unroll
-            for (int i = 0; i < NX; ++i) gzv[i] = fma(qp_mask(i, idx), lo ? -c : c, gzv[i]);
+            for (int i = 0; i < NX; ++i) gzv[i] = bacc(i, b, lo ? -c : c, gzv[i]);
         } else if (r < C::L.R_GRP) {
             const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
 #pragma unroll
@@ -1946,9 +2001,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                         for (int j = 0; j < NU; ++j) Huu[i * NU + j] += (((r >> i) ^ (r >> j)) & 1) ? -Dr : Dr;
                 }
             } else if (r < C::L.R_OBS) {
-                const int idx = bidx[(r - C::L.R_BOX) >> 1];
+                const int b = (r - C::L.R_BOX) >> 1;
 #pragma unroll
-                for (int i = 0; i < NX; ++i) dbox[i] = fma(qp_mask(i, idx), Dr, dbox[i]);
+                for (int i = 0; i < NX; ++i) dbox[i] = bacc(i, b, Dr, dbox[i]);
             } else if (r < C::L.R_GRP) {
                 const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
                 Haa[g] += Dr;
@@ -2382,7 +2437,7 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     const double tol = T.tol > 0 ? T.tol : 1e-9;
 
     // ------------------------------------------------------------------ IPM iterations
-    const long long cyc_all0 = __builtin_amdgcn_s_memtime();
+    const long long cyc_all0 = TRACE ? __builtin_amdgcn_s_memtime() : 0;
     double dres_best = 1e300, pres_best = 1e300;
     stamp(-1);
     // the residuals are evaluated once more after the last step: an iterate that reaches the
@@ -2630,8 +2685,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         dres_best = fmin(dres_best, dres);
         pres_best = fmin(pres_best, pres);
         // diagnostics trace, residual part (written here so these values die before the direction phases)
-        if (a.trace && agent == a.trace_agent && lane == 0 && it < a.trace_cap) {
-            double* tr_ = a.trace + 8 * it;
+        if (trace && agent == a.trace_agent && lane == 0 && it < a.trace_cap) {
+            double* tr_ = trace + 8 * it;
             tr_[0] = pres; tr_[1] = dres; tr_[2] = gap; tr_[3] = pobj * osc; tr_[7] = mu;
         }
         // assemble's C_{t-1}: in flight across the scaling arithmetic (the residual phase's copy is dead by now)
@@ -3040,8 +3095,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 break;
             }
         }
-        if (a.trace && agent == a.trace_agent && lane == 0 && it < a.trace_cap) {
-            double* tr_ = a.trace + 8 * it;
+        if (trace && agent == a.trace_agent && lane == 0 && it < a.trace_cap) {
+            double* tr_ = trace + 8 * it;
             tr_[4] = aa; tr_[5] = al; tr_[6] = sgm;
         }
         // ---- update
@@ -3093,8 +3148,8 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 #pragma unroll
     for (int r = 0; r < NR; ++r) cst(C::L.C_WL + r, l_(r));
     cst(C::L.C_WY, lane < 2 * NX ? lds[V_YI + lane] : 0.0);
-    if (a.trace && agent == a.trace_agent && lane == 0) {
-        double* dd = a.trace + 8 * a.trace_cap;
+    if (trace && agent == a.trace_agent && lane == 0) {
+        double* dd = trace + 8 * a.trace_cap;
         dd[0] = 0.0; dd[1] = 0.0; dd[2] = (double)(__builtin_amdgcn_s_memtime() - cyc_all0);
         dd[3] = fail_code;
         for (int k = 0; k < 16; ++k) dd[4 + k] = lds[V_ST + k];
@@ -3135,18 +3190,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         a.obj[agent] = pobj * osc;
         a.status[agent] = status;
         a.iters[agent] = it;
-        if (a.trace && a.trace_agent < 0) a.trace[agent] = fail_code;  // diagnostics: every agent's exit code
+        if (trace && a.trace_agent < 0) trace[agent] = fail_code;  // diagnostics: every agent's exit code
     }
 }
 
 #ifndef __HIPCC_RTC__
 // launch helpers (qp_capi.hip picks the instantiation)
-template <class C, int KC = 0>
+template <class C, int KC = 0, class F = QPFlagsRT>
 int qp_launch(const QPArgs& a, hipStream_t st) {
     if (KC > 0 && a.T.K != KC) return set_error(SCVX_EINVAL, "qp: K-specialised instantiation launched at another K");
     const size_t lds = sizeof(double) * (size_t)C::L.lds_doubles(a.T.K);
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)qp_ipm_kernel<C, KC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((qp_ipm_kernel<C, KC>), dim3(a.N), dim3(WAVE), lds, st, a);
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)qp_ipm_kernel<C, KC, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((qp_ipm_kernel<C, KC, F>), dim3(a.N), dim3(WAVE), lds, st, a);
     return check_launch("qp_ipm_kernel");
 }
 #endif
