@@ -688,13 +688,37 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             }
             pstamp(15);
             // ---- phase 1: T1 = P'A, T2 = P'Bt, W1 = A'Pi', W2 = Bt'Pi', u = P'e, xe += Pi''e
-            if constexpr (CMP) qp_phase_c<NX, R1, E1 - NX, E1>(lds, qs, blast, wb, fbo, a1);
-            else qp_phase<NX, R1, E1 - NX, E1>(lds, q1, blast, wb, fbo, a1);
+            // FS_E (n <= 8): phase 2's and phase 4's L operands and bases are read ahead of the fence in front of
+            // them (qp_factor_phase.hpp FS_C); only their R operands are the previous phase's output.  A wave's DS
+            // instructions execute in order, so a read issued here sees every write issued before it and none after.
+            constexpr int FSM = qp_fs_mask(NX, NU, C::L.NB, C::L.NO, C::L.NC);
+            constexpr bool FS_E = (FSM & QP_FS_C) != 0;
+            QPOps<NX, CMP ? 1 : R2> o2;
+            QPOps<NU, CMP ? 1 : R4> o4;
+            if constexpr (CMP) {
+                qp_phase_c<NX, R1, E1 - NX, E1>(lds, qs, blast, wb, fbo, a1);
+            } else if constexpr (FS_E) {
+                QPOps<NX, R1> o1;
+                qp_phase_issue<3>(lds, q1, o1);
+                // phase 2's L (P_A, P_BT) and bases (P_Q, P_S, P_R): packet entries, last written by the previous
+                // stage's pf_store (the first stage's before the loop); phase 1 writes T1, T2, W1, W2 only.  Behind
+                // phase 1's own reads: the returns come back in issue order.
+                qp_phase_issue<1>(lds, q2, o2);
+                qp_phase_finish<NX, R1, E1 - NX, E1>(lds, q1, blast, wb, fbo, a1, o1);
+            } else {
+                qp_phase<FSM, NX, R1, E1 - NX, E1>(lds, q1, blast, wb, fbo, a1);
+            }
             wsync();
             pstamp(11);
             // ---- phase 2: Qh = Q + A'T1, Sh = S' + Bt'T1, Rh = R + Bt'T2
-            if constexpr (CMP) qp_phase_c<NX, R2, 0, 0>(lds, qs + R1, blast, wb, fbo, a2);
-            else qp_phase<NX, R2, 0, 0>(lds, q2, blast, wb, fbo, a2);
+            if constexpr (CMP) {
+                qp_phase_c<NX, R2, 0, 0>(lds, qs + R1, blast, wb, fbo, a2);
+            } else if constexpr (FS_E) {
+                qp_phase_issue<2>(lds, q2, o2);   // R = T1, T2: phase 1's output
+                qp_phase_finish<NX, R2, 0, 0>(lds, q2, blast, wb, fbo, a2, o2);
+            } else {
+                qp_phase<FSM, NX, R2, 0, 0>(lds, q2, blast, wb, fbo, a2);
+            }
             wsync();
             pstamp(12);
             // ---- phase 3: Rh = L D L' in registers (every lane); [K | kappa] = -Rh^-1 [Sh | W2]
@@ -709,6 +733,10 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
                 double Lm[NU * NU], dinv[NU];
 #pragma unroll
                 for (int e = 0; e < NU * NU; ++e) Lm[e] = lds[C::L.F_RH + e];
+                // FS_E: phase 4's L (Sh: last written by phase 2, W2: by phase 1, Btr: a packet entry, last written by
+                // the previous stage's pf_store) and bases (Qh: phase 2, W1: phase 1, A: packet) go out behind the Rh
+                // reads, in flight across the pivot chain; this phase writes F_KK only
+                if constexpr (FS_E) qp_phase_issue<1>(lds, q4, o4);
                 // stiff trust-region facets (STF): Rhat arrives without the facets.  Those whose weight exceeds
                 // QP_STIFF x its largest diagonal stay explicit when there are at most m-1 of them and no two are
                 // opposite (a face or an edge of the L1 ball: they leave a complement whose small curvature the fold
@@ -1004,8 +1032,14 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             wsync();
             pstamp(13);
             // ---- phase 4: P = Qh + Sh'K, Pi = W1 + Sh'kappa, M += W2'kappa, Acl = A + Bt K
-            if constexpr (CMP) qp_phase_c<NU, R4, 2 * NX * NX, 3 * NX * NX>(lds, qs + R1 + R2, blast, wb, fbo, a4);
-            else qp_phase<NU, R4, 2 * NX * NX, 3 * NX * NX>(lds, q4, blast, wb, fbo, a4);
+            if constexpr (CMP) {
+                qp_phase_c<NU, R4, 2 * NX * NX, 3 * NX * NX>(lds, qs + R1 + R2, blast, wb, fbo, a4);
+            } else if constexpr (FS_E) {
+                qp_phase_issue<2>(lds, q4, o4);   // R = [K | kappa]: phase 3's output
+                qp_phase_finish<NU, R4, 2 * NX * NX, 3 * NX * NX>(lds, q4, blast, wb, fbo, a4, o4);
+            } else {
+                qp_phase<FSM, NU, R4, 2 * NX * NX, 3 * NX * NX>(lds, q4, blast, wb, fbo, a4);
+            }
             if (ts > 0) pf_store(ts - 1, cb);
             wsync();
             pstamp(14);
