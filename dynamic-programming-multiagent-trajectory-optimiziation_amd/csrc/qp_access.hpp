@@ -80,6 +80,12 @@ __device__ __forceinline__ int qp_opaque(int v) {
     asm volatile("" : "+v"(v));
     return v;
 }
+// a double made opaque where it is defined (not volatile: it orders nothing).  A product pinned this way stays rounded
+// on its own: the backend cannot contract it into a sum that consumes it.
+__device__ __forceinline__ double qp_rounded(double v) {
+    asm("" : "+v"(v));
+    return v;
+}
 // 1.0 if a == b else 0.0, opaque to the optimiser: selecting an array element by a runtime
 // index with this mask stays arithmetic (a compare/select chain is turned back into a
 // dynamically indexed private array, i.e. scratch memory)

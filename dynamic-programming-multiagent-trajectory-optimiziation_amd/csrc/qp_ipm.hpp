@@ -89,6 +89,11 @@ struct QPFlags {
 #define QP_INSN_STEPS 3
 #endif
 
+// lever of DESIGN §3.3 "Lane guards and spill reloads" (bit A = 1; -DQP_NA_STEPS=0 builds without it, tools/build_variant.sh)
+#ifndef QP_NA_STEPS
+#define QP_NA_STEPS 1
+#endif
+
 // KC: the node count K at compile time (0: T.K at run time).  With KC set, every workspace offset (the column stride,
 // the packet and factor-block bases), the LDS offsets of the K-sized blocks and the chunk geometry are constants;
 // the workspace layout and the arithmetic are those of the KC = 0 instantiation of the same class (a warm start
@@ -427,6 +432,17 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     constexpr bool RT_ON = NX <= 8 && NS <= 8 && NV == 0;
     constexpr bool RT_A = RT_ON && (QP_RT_STEPS & 1), RT_B = RT_ON && (QP_RT_STEPS & 2),
                    RT_C = RT_ON && (QP_RT_STEPS & 4), RT_F = RT_ON && (QP_RT_STEPS & 8);
+    // Lane guards of the row loops (DESIGN §3.3 "Lane guards and spill reloads"); no floating-point expression changes.
+    // Every row's predicate is row_on(r) = ineq && row_in(r), and row_in(r) is a constant (flag-specialised classes),
+    // wave-uniform (r < n_box, r < n_obs) or, for the collision rows alone, per lane.
+    //   NA_A  a row loop whose body runs only where row_on(r) holds runs under one `if (ineq)` with row_in(r) inside:
+    //         one exec region per loop instead of one per row.  assemble's barrier weights D_r = l_r / s_r are computed
+    //         on all 64 lanes: a row that is off in a lane holds s = 1, l = 0 there (set at the starting point, never
+    //         updated), so the quotient is the +0.0 that the guarded form selected.
+    // Only the flag-specialised instantiations (whose rows live in LDS): there the step adds no scratch and no vector
+    // spill; in the runtime-flag instantiations of the same classes it did (DESIGN, the static table).
+    // (diagnostics builds: -DQP_NA_STEPS=0 builds without the step, tools/build_variant.sh)
+    constexpr bool NA_A = FS && RT_ON && !C::L.ROWG && (QP_NA_STEPS & 1);
 
     // ------------------------------------------------------------------ factor sweep
     // Stage inputs (Q, S, R, e of the node phase; A, Bt, C_{t-1}) are in packet t; Acl goes to
@@ -1932,6 +1948,17 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         if (r < C::L.R_GRP) return (r - C::L.R_COL) < ccount;
         return grp_on(r - C::L.R_GRP);
     };
+    // row_on(r) inside an `if (ineq)` region: row_on(r) == ineq && row_in(r) (ccount is 0 where ineq is false)
+    auto row_in = [&](int r) __attribute__((always_inline)) -> bool {
+        if (r < C::L.R_BOX) return true;
+        if (r < C::L.R_OBS) return ((r - C::L.R_BOX) >> 1) < nbox;
+        if (r < C::L.R_COL) return (r - C::L.R_OBS) < nobs;
+        if (r < C::L.R_GRP) return (r - C::L.R_COL) < ccount;
+        return (r - C::L.R_GRP) < NO ? (r - C::L.R_GRP) < nobs : has_coll;
+    };
+    // the lanes a row loop runs on (NA_A: one mask per loop, the rows' own switches inside) and row r's switch there
+    auto rows_lane = [&]() __attribute__((always_inline)) -> bool { return NA_A ? ineq : true; };
+    auto row_here = [&](int r) __attribute__((always_inline)) -> bool { return NA_A ? row_in(r) : row_on(r); };
     // g + m c with m = 1.0 where state component i is box b's, else 0.0: fma(m, c, g) with an opaque mask for a
     // runtime index (qp_mask).  With the index a compile-time constant the masks are literals: fma(1.0, c, g) is
     // c + g rounded once (qp_add_nc: c, often a product, must stay rounded on its own as the fma's operand was), and
@@ -2022,9 +2049,14 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         double Haa[NGA], Hpa[NGA][3], D0[NGA];
 #pragma unroll
         for (int g = 0; g < NGA; ++g) { Haa[g] = 0.0; D0[g] = 0.0; Hpa[g][0] = Hpa[g][1] = Hpa[g][2] = 0.0; }
+        // D_r = l_r / s_r (1 at unit scaling) where the row is on, else 0.  NA_A: the quotient on every lane -- an off
+        // row's s = 1, l = 0 give +0.0 -- and pinned (qp_rounded): the guarded form's value reached the sums below
+        // through a select, so the quotient's last product was never contracted into them
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-            const double Dr = row_on(r) ? (unit ? 1.0 : qp_div(l_(r), s_(r))) : 0.0;
+            double Dr;
+            if constexpr (NA_A) Dr = unit ? (row_on(r) ? 1.0 : 0.0) : qp_rounded(qp_div(l_(r), s_(r)));
+            else Dr = row_on(r) ? (unit ? 1.0 : qp_div(l_(r), s_(r))) : 0.0;
             if (r < C::L.R_BOX) {
                 if constexpr (C::L.STF) {
                     Dfc[r] = Dr;   // folded below, all but the stiff ones
@@ -2071,7 +2103,9 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         }
 #pragma unroll
         for (int r = C::L.R_OBS; r < C::L.R_GRP; ++r) {
-            const double Dr = row_on(r) ? (unit ? 1.0 : qp_div(l_(r), s_(r))) : 0.0;
+            double Dr;
+            if constexpr (NA_A) Dr = unit ? (row_on(r) ? 1.0 : 0.0) : qp_rounded(qp_div(l_(r), s_(r)));
+            else Dr = row_on(r) ? (unit ? 1.0 : qp_div(l_(r), s_(r))) : 0.0;
             const int q = r - C::L.R_OBS, g = q < NO ? q : NO;
             double c[3];
 #pragma unroll
@@ -2619,18 +2653,20 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         for (int i = 0; i < NV; ++i) rp[i] -= vact ? vn[i] : 0.0;   // + nu_t in the dynamics
 #pragma unroll
         for (int i = 0; i < NX; ++i) pres = fmax(pres, fabs(rp[i]));
+        if (rows_lane()) {
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            double gz, h;
-            row_eval(r, z, av, gz, h);
-            if (row_on(r)) {
-                const double rcr = gz + s_(r) - h;
-                pres = fmax(pres, fabs(rcr));
-                nb = fmax(nb, fabs(h));
-                nsl = fmax(nsl, s_(r));
-                nzd = fmax(nzd, l_(r));
-                gap += s_(r) * l_(r);
-                row_accT(r, l_(r), rd, rda);
+            for (int r = 0; r < NR; ++r) {
+                double gz, h;
+                row_eval(r, z, av, gz, h);
+                if (row_here(r)) {
+                    const double rcr = gz + s_(r) - h;
+                    pres = fmax(pres, fabs(rcr));
+                    nb = fmax(nb, fabs(h));
+                    nsl = fmax(nsl, s_(r));
+                    nzd = fmax(nzd, l_(r));
+                    gap += s_(r) * l_(r);
+                    row_accT(r, l_(r), rd, rda);
+                }
             }
         }
         if (soc) {
@@ -2854,28 +2890,30 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             for (int r = 0; r < NR; ++r) cpv[r] = corr ? cpv[r] : 0.0;
 #pragma unroll
             for (int g = 0; g < NGA; ++g) r1a[g] = -gweight(g);
+            if (rows_lane()) {
 #pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                if (row_on(r)) {
-                    double gz, h;
-                    row_eval(r, z, av, gz, h);
-                    const double rcr = gz + s_(r) - h;
-                    row_accA(r, -l_(r), r1a);  // -rd, group part: -(w_g - sum lambda)
-                    double c = -qp_div(rco_of(r, corr) + l_(r) * rcr, s_(r));
-                    if constexpr (C::L.STF) {
-                        if (r < C::L.R_BOX) {   // a stiff facet: its rho = -(rco / l + rc) goes to the stage system
-                            const double rho_f = -(rco_of(r, corr) / l_(r) + rcr);
-                            bool st = false;
+                for (int r = 0; r < NR; ++r) {
+                    if (row_here(r)) {
+                        double gz, h;
+                        row_eval(r, z, av, gz, h);
+                        const double rcr = gz + s_(r) - h;
+                        row_accA(r, -l_(r), r1a);  // -rd, group part: -(w_g - sum lambda)
+                        double c = -qp_div(rco_of(r, corr) + l_(r) * rcr, s_(r));
+                        if constexpr (C::L.STF) {
+                            if (r < C::L.R_BOX) {   // a stiff facet: its rho = -(rco / l + rc) goes to the stage system
+                                const double rho_f = -(rco_of(r, corr) / l_(r) + rcr);
+                                bool st = false;
 #pragma unroll
-                            for (int i = 0; i < C::L.PM; ++i) {
-                                const bool m_ = sfr[i] == (double)r;
-                                rhs_s[i] = m_ ? rho_f : rhs_s[i];
-                                st |= m_;
+                                for (int i = 0; i < C::L.PM; ++i) {
+                                    const bool m_ = sfr[i] == (double)r;
+                                    rhs_s[i] = m_ ? rho_f : rhs_s[i];
+                                    st |= m_;
+                                }
+                                c = st ? 0.0 : c;
                             }
-                            c = st ? 0.0 : c;
                         }
+                        row_accT(r, c, r1, r1a);
                     }
-                    row_accT(r, c, r1, r1a);
                 }
             }
 #pragma unroll
@@ -2993,33 +3031,35 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
         // live direction (0 * x poisons the sum).
         auto max_step = [&](bool corr, double* quad, double& probe) __attribute__((always_inline)) {
             double bn = 1e300, bd = 1.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, pr = 0.0;
+            if (rows_lane()) {
 #pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                if (row_on(r)) {
-                    double dsr, dlr;
-                    row_dir(r, corr, dsr, dlr);
-                    const double sr = s_(r), lr = l_(r);
-                    const bool c1 = dsr < 0.0 && sr * bd < bn * -dsr;
-                    bn = c1 ? sr : bn;
-                    bd = c1 ? -dsr : bd;
-                    const bool c2 = dlr < 0.0 && lr * bd < bn * -dlr;
-                    bn = c2 ? lr : bn;
-                    bd = c2 ? -dlr : bd;
-                    q0 = fma(sr, lr, q0);
-                    q1 += fma(sr, dlr, lr * dsr);
-                    q2 = fma(dsr, dlr, q2);
-                    pr += 0.0 * (dsr + dlr);
-                    if constexpr (RT_A) {
-                        if (!corr) {
-                            // (the product pinned: kept in a register for the corrector's rhs it must stay the rounded
-                            // product that the store holds, not contract into the rhs's subtraction)
-                            double pp = dsr * dlr;
-                            hold(&pp, 1);
-                            cpv[r] = pp;
-                            cst(C::L.C_CP + r, pp);
+                for (int r = 0; r < NR; ++r) {
+                    if (row_here(r)) {
+                        double dsr, dlr;
+                        row_dir(r, corr, dsr, dlr);
+                        const double sr = s_(r), lr = l_(r);
+                        const bool c1 = dsr < 0.0 && sr * bd < bn * -dsr;
+                        bn = c1 ? sr : bn;
+                        bd = c1 ? -dsr : bd;
+                        const bool c2 = dlr < 0.0 && lr * bd < bn * -dlr;
+                        bn = c2 ? lr : bn;
+                        bd = c2 ? -dlr : bd;
+                        q0 = fma(sr, lr, q0);
+                        q1 += fma(sr, dlr, lr * dsr);
+                        q2 = fma(dsr, dlr, q2);
+                        pr += 0.0 * (dsr + dlr);
+                        if constexpr (RT_A) {
+                            if (!corr) {
+                                // (the product pinned: kept in a register for the corrector's rhs it must stay the rounded
+                                // product that the store holds, not contract into the rhs's subtraction)
+                                double pp = dsr * dlr;
+                                hold(&pp, 1);
+                                cpv[r] = pp;
+                                cst(C::L.C_CP + r, pp);
+                            }
+                        } else {
+                            if (!corr) cst(C::L.C_CP + r, dsr * dlr);
                         }
-                    } else {
-                        if (!corr) cst(C::L.C_CP + r, dsr * dlr);
                     }
                 }
             }
@@ -3134,13 +3174,15 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
             tr_[4] = aa; tr_[5] = al; tr_[6] = sgm;
         }
         // ---- update
+        if (rows_lane()) {
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            if (row_on(r)) {
-                double dsr, dlr;
-                row_dir(r, true, dsr, dlr);
-                s_set(r, s_(r) + al * dsr);
-                l_set(r, l_(r) + al * dlr);
+            for (int r = 0; r < NR; ++r) {
+                if (row_here(r)) {
+                    double dsr, dlr;
+                    row_dir(r, true, dsr, dlr);
+                    s_set(r, s_(r) + al * dsr);
+                    l_set(r, l_(r) + al * dlr);
+                }
             }
         }
         if constexpr (NV > 0) {
