@@ -14,6 +14,8 @@ kernels run on torch's current HIP stream, nothing falls back to the CPU.
                            (SCvx/optimization/sc_problem.py:15-83, agent_solver.py:78-102)
     fleet_separation       continuous-time closest approach of every agent to every other (rollout_dense +
                            separation_scan; no reference counterpart)
+    intersample_pair_rows  the same scan as QP rows: per (agent, segment) the neighbours that pass too close between
+    append_collision_rows  two nodes, appended to collision_rows' node rows (CouplingSpec.intersample_S)
     pair_min_distance      node-level pairwise / agent-obstacle minimum distances
     obstacle_min_distance  (SCvx/utils/analysis.py:10-62)
 """
@@ -40,7 +42,7 @@ QUAD_PARAMS = (1.0, 9.81, 0.02, 0.02, 0.04)
 
 __all__ = ["model_dims", "model_id", "default_nsub", "foh_batched", "jacobi_update", "jacobi_update_global", "integrate_nonlinear", "collision_rows", "collision_check", "qp_solve_batched", "QPSpec", "SCPSpec", "SCPSolver", "slab_update",
            "intersample_batched", "rollout_dense", "separation_scan", "fleet_separation", "pair_min_distance",
-           "obstacle_min_distance",
+           "obstacle_min_distance", "intersample_pair_rows", "append_collision_rows",
            "disc_stride", "unpack_disc", "ScvxError", "MODEL_DIMS", "DEFAULT_NSUB"]
 
 
@@ -790,6 +792,75 @@ def fleet_separation(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=No
     out["min"] = float(out["sep"][i, k].item())
     out["argmin"] = (i, int(out["j"][i, k].item()), k, float(out["tau"][i, k].item())) if X.shape[0] > 1 else None
     return out
+
+
+def intersample_pair_rows(P_all, L_all, i0, n_local, R, cull, J=2, stream=None, prune=True):
+    """Inter-sample collision records of local agents [i0, i0+n_local) on the dense samples P_all
+    (N_total,K-1,S+1,3) / L_all (N_total,K-1) of rollout_dense (scvx_intersample_pair_rows_batched): per (agent,
+    segment) the J neighbours whose chord closest approach lies strictly between the two nodes (0 < alpha' < 1), is
+    closer than cull and is not zero, nearest first, ties to the lower j.  Returns device tensors rec
+    (n_local,K-1,J,4) = (g, v) with g = c / dist the unit relative position at the closest approach and
+    v = 2R - dist, nbr (n_local,K-1,J) int32 the neighbour (-1 past count), alpha (n_local,K-1,J) = alpha' and count
+    (n_local,K-1) int32.  prune=False (tests) disables the skip of far neighbours; the outputs are bit-identical."""
+    torch = _torch()
+    if P_all.dim() != 4 or P_all.shape[3] != 3 or P_all.shape[2] < 2 or tuple(L_all.shape) != tuple(P_all.shape[:2]):
+        raise ValueError("intersample_pair_rows: P_all (N_total,K-1,S+1,3) and L_all (N_total,K-1) expected")
+    N_total, Km1, S = P_all.shape[0], P_all.shape[1], P_all.shape[2] - 1
+    i0, n_local, J = int(i0), int(n_local), int(J)
+    if S > 16 or not 1 <= Km1 <= 63 or i0 < 0 or n_local < 0 or i0 + n_local > N_total:
+        raise ValueError(f"intersample_pair_rows: S <= 16, 2 <= K <= 64 and 0 <= i0, i0 + n_local <= N_total required; "
+                         f"got S={S}, K-1={Km1}, i0={i0}, n_local={n_local}, N_total={N_total}")
+    if not 1 <= J <= 8 or not float(cull) > 0.0:
+        raise ValueError(f"intersample_pair_rows: 1 <= J <= 8 and cull > 0 required, got J={J}, cull={cull}")
+    dev = P_all.device
+    rec = torch.empty((n_local, Km1, J, 4), dtype=torch.float64, device=dev)
+    nbr = torch.empty((n_local, Km1, J), dtype=torch.int32, device=dev)
+    alpha = torch.empty((n_local, Km1, J), dtype=torch.float64, device=dev)
+    count = torch.empty((n_local, Km1), dtype=torch.int32, device=dev)
+    rc = lib().scvx_intersample_pair_rows_batched(Km1 + 1, S, N_total, _dev(P_all, name="P_all"),
+                                                  _dev(L_all, name="L_all"), i0, n_local, float(R), float(cull), J,
+                                                  _dev(rec, name="rec"), _dev(nbr, torch.int32, "nbr"),
+                                                  _dev(alpha, name="alpha"), _dev(count, torch.int32, "count"),
+                                                  0 if prune else 1, _stream(stream))
+    check(rc, "scvx_intersample_pair_rows_batched")
+    return dict(rec=rec, nbr=nbr, alpha=alpha, count=count)
+
+
+def append_collision_rows(X_all, i0, rec, count_seg, rows, count, pos_dim=3, idx=None, overflow=None, check_index=True,
+                          stream=None):
+    """Append the records of intersample_pair_rows behind the node rows of collision_rows
+    (scvx_collision_rows_append_batched): a record of segment k becomes the rows (g, b = v + g . pbar_t) at nodes
+    t = k and t = k+1, pbar = X_all (N_total,K,n) the current iterate; per node segment t's records first, then
+    segment t-1's, none at node K-1.  rows (>= n,K,j_max,pos_dim+1) and count (>= n,K) int32 are updated in place
+    (their leading n entries); rows past j_max are dropped and counted in overflow (a (1,) int32 device tensor that
+    accumulates; a zeroed one is made when None).  idx None: the n = rec.shape[0] agents i0, i0+1, ...; idx (device
+    int32): agent a is global agent idx[a], as collision_rows_indexed, and reads rec / count_seg [idx[a] - i0]
+    (check_index=False skips the range check of idx, a device -> host read).  Returns (rows, count, overflow)."""
+    torch = _torch()
+    N_total, K, n_x = X_all.shape
+    i0, pos_dim = int(i0), int(pos_dim)
+    if rec.dim() != 4 or tuple(rec.shape[1:2] + rec.shape[3:]) != (K - 1, 4) or tuple(count_seg.shape) != tuple(rec.shape[:2]):
+        raise ValueError(f"append_collision_rows: rec (n,{K - 1},J,4) and count_seg (n,{K - 1}) expected")
+    n_rec, J = int(rec.shape[0]), int(rec.shape[2])
+    n = n_rec if idx is None else int(idx.shape[0])
+    if not 1 <= J <= 8 or not 2 <= K <= 64 or not 1 <= pos_dim <= min(3, n_x) or i0 < 0 or i0 + n_rec > N_total:
+        raise ValueError(f"append_collision_rows: 1 <= J <= 8, 2 <= K <= 64, 1 <= pos_dim <= {min(3, n_x)} and "
+                         f"0 <= i0, i0 + n <= N_total required; got J={J}, K={K}, pos_dim={pos_dim}, i0={i0}")
+    if rows.dim() != 4 or rows.shape[0] < n or tuple(rows.shape[1:2] + rows.shape[3:]) != (K, pos_dim + 1) or \
+            count.dim() != 2 or count.shape[0] < n or count.shape[1] != K or not 1 <= rows.shape[2] <= 32:
+        raise ValueError(f"append_collision_rows: rows (>= {n},{K},j_max <= 32,{pos_dim + 1}) and count (>= {n},{K}) expected")
+    if idx is not None and check_index and n and (int(idx.min()) < i0 or int(idx.max()) >= i0 + n_rec):
+        raise ValueError("append_collision_rows: idx outside the agents [i0, i0 + rec.shape[0]) the records cover")
+    if overflow is None:
+        overflow = torch.zeros((1,), dtype=torch.int32, device=X_all.device)
+    rc = lib().scvx_collision_rows_append_batched(K, pos_dim, n_x, N_total, _dev(X_all, name="X_all"), i0,
+                                                  _dev(idx, torch.int32, "idx") if idx is not None else None, n, J,
+                                                  _dev(rec, name="rec"), _dev(count_seg, torch.int32, "count_seg"),
+                                                  int(rows.shape[2]), _dev(rows, name="rows"),
+                                                  _dev(count, torch.int32, "count"),
+                                                  _dev(overflow, torch.int32, "overflow"), _stream(stream))
+    check(rc, "scvx_collision_rows_append_batched")
+    return rows, count, overflow
 
 
 def pair_min_distance(X, rows=None, stream=None):

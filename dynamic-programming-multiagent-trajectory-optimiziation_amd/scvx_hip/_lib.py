@@ -28,7 +28,8 @@ EXPORTS = ("scvx_version", "scvx_last_error", "scvx_foh_batched", "scvx_integrat
            "scvx_rtc_model_source", "scvx_rtc_model_log", "scvx_rtc_model_destroy", "scvx_rtc_foh_batched",
            "scvx_rtc_integrate_nonlinear_batched", "scvx_rtc_subproblem_compile", "scvx_rtc_intersample_batched",
            "scvx_jacobi_update_costs_batched", "scvx_jacobi_global_rule", "scvx_rollout_dense_batched",
-           "scvx_separation_scan_batched", "scvx_pair_min_distance_batched", "scvx_obstacle_min_distance_batched")
+           "scvx_separation_scan_batched", "scvx_pair_min_distance_batched", "scvx_obstacle_min_distance_batched",
+           "scvx_intersample_pair_rows_batched", "scvx_collision_rows_append_batched")
 SCVX_MAX_MODEL_PARAMS, SCVX_RTC_MAX_NX, SCVX_RTC_MAX_NU = 16, 16, 8
 
 
@@ -127,6 +128,14 @@ def lib():
         L.scvx_separation_scan_batched.argtypes = [i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp]
         L.scvx_pair_min_distance_batched.argtypes = [i32, i32, i32, i32, vp, vp, vp]
         L.scvx_obstacle_min_distance_batched.argtypes = [i32, i32, i32, vp, i32, vp, vp, dbl, vp, vp]
+        # added to revision 7 without a bump (purely additive): a library built before them is named plainly
+        if not hasattr(L, "scvx_intersample_pair_rows_batched"):
+            raise ImportError(f"{LIB_PATH} lacks the inter-sample collision rows entry points: rebuild it "
+                              f"(`make -C {os.path.dirname(HERE)}`)")
+        L.scvx_intersample_pair_rows_batched.argtypes = [i32, i32, i32, vp, vp, i32, i32, dbl, dbl, i32, vp, vp, vp, vp,
+                                                         i32, vp]
+        L.scvx_collision_rows_append_batched.argtypes = [i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp,
+                                                         vp, vp]
         cpp = ctypes.POINTER(ctypes.c_char_p)
         L.scvx_rtc_model_create.argtypes = [i32, i32, cpp, cpp, cpp, ctypes.c_char_p, ctypes.POINTER(vp)]
         L.scvx_rtc_model_source.argtypes = [vp]

@@ -15,8 +15,9 @@ import dataclasses
 from dataclasses import dataclass
 from typing import Optional
 
-from . import (QPSolver, QPSpec, collision_check, collision_rows, collision_rows_indexed, default_nsub, fleet_separation,
-               foh_batched, jacobi_update, jacobi_update_global, model_dims)
+from . import (QPSolver, QPSpec, append_collision_rows, collision_check, collision_rows, collision_rows_indexed,
+               default_nsub, fleet_separation, foh_batched, intersample_pair_rows, jacobi_update, jacobi_update_global,
+               model_dims, rollout_dense)
 
 
 def balanced_order(iters, world):
@@ -58,6 +59,16 @@ class HipBackend:
     def collision_check(self, X_all, i0, X_new, slack, R, pos_dim, tol):
         return collision_check(X_all, i0, X_new, slack, R, pos_dim, tol)
 
+    def intersample_pair_rows(self, model, X, U, sigma, S, nsub, pos_dim, R, cull, J):
+        """(rec, count_seg) of every agent of the iterate (X, U): the dense roll-out, then the pair-rows scan."""
+        P, L = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim)
+        out = intersample_pair_rows(P, L, 0, X.shape[0], R, cull, J)
+        return out["rec"], out["count"]
+
+    def append_collision_rows(self, X_all, i0, idx, rec, count_seg, rows, count, pos_dim, overflow):
+        return append_collision_rows(X_all, i0, rec, count_seg, rows, count, pos_dim, idx=idx, overflow=overflow,
+                                     check_index=False)   # idx comes from this rank's own agents
+
     def qp_solver(self, spec, N, device):
         return QPSolver(spec, N, device=device)
 
@@ -76,12 +87,21 @@ class CouplingSpec:
     agents that violate one are re-solved with the j_max_hi nearest rows.  The culled problem is a
     relaxation of the reference's, so a solution that satisfies every row IS the reference's; agents
     still violating after the re-solve (more binding neighbours than j_max_hi) are counted in
-    JacobiSCvx.last_check["overflow"]."""
+    JacobiSCvx.last_check["overflow"].
+
+    intersample_S > 0 adds continuous-time rows (single rank): every step the iterate is rolled out with
+    intersample_S samples per segment, the intersample_J neighbours per (agent, segment) that pass closer than
+    intersample_cull strictly between two nodes each become two node rows, and these are appended behind the node
+    rows.  QPSpec.j_max (and j_max_hi in the re-solve) is then the total capacity per node: the node-level rows
+    get j_max - 2 intersample_J of it.  Build-side option; the reference constrains the nodes only."""
     R: float = 2.3              # agent radius (dist_scvx_3d.py:211); rows use 2R
     cull_radius: float = 0.0    # <= 0: every neighbour (exact reference semantics)
     check: bool = True          # evaluate every reference row at the solution
     j_max_hi: int = 32          # nearest rows of the re-solve (the largest QP capacity class)
     check_tol: float = 1e-7     # row violation threshold (metres)
+    intersample_S: int = 0      # dense samples per segment of the continuous-time rows; 0: off, nothing changes
+    intersample_J: int = 2      # neighbours kept per (agent, segment)
+    intersample_cull: float = 0.0   # pairs farther apart than this give no row; <= 0: 3R
 
 
 class JacobiSCvx:
@@ -169,6 +189,25 @@ class JacobiSCvx:
                                     device=self.device)
             self.count = torch.zeros((self.N, spec.K), dtype=torch.int32, device=self.device)
         self._hi = None   # re-solve buffers of the full-row check (allocated at the first violation)
+        self._is = None   # continuous-time rows (CouplingSpec.intersample_S > 0): settings and buffers
+        if coupling is not None and coupling.intersample_S > 0:
+            if self.world > 1:
+                raise NotImplementedError("CouplingSpec.intersample_S at world > 1 needs the all-gather of the dense "
+                                          "samples P (and L) across ranks before the scan, which is not implemented")
+            S, J = int(coupling.intersample_S), int(coupling.intersample_J)
+            if not 1 <= S <= 16 or not 1 <= J <= 8:
+                raise ValueError(f"CouplingSpec: 1 <= intersample_S <= 16 and 1 <= intersample_J <= 8 required, got "
+                                 f"{S}, {J}")
+            j_node = spec.j_max - 2 * J
+            if j_node < 1:   # (the re-solve runs only at j_max_hi > j_max, which then leaves room as well)
+                raise ValueError(f"CouplingSpec.intersample_S > 0: QPSpec.j_max = {spec.j_max} is the total capacity "
+                                 f"per node and must leave at least one node-level row next to the 2 x intersample_J = "
+                                 f"{2 * J} continuous-time rows")
+            cull = float(coupling.intersample_cull) if coupling.intersample_cull > 0 else 3.0 * coupling.R
+            self._is = dict(S=S, J=J, cull=cull, j_node=j_node, rec=None, count_seg=None,
+                            rows_node=torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
+                                                  device=self.device),
+                            overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
 
     def _hi_buffers(self):
         """Rows, counts and a QPSolver at j_max_hi sized for all N local agents, allocated once: a re-solve
@@ -180,6 +219,9 @@ class JacobiSCvx:
                                              device=self.device),
                             count=torch.zeros((self.N, spec.K), dtype=torch.int32, device=self.device),
                             solver=self.backend.qp_solver(spec_hi, self.N, self.device))
+            if self._is is not None:   # the node-level share of j_max_hi, before the continuous-time rows join it
+                self._hi["rows_node"] = torch.zeros((self.N, spec.K, c.j_max_hi - 2 * self._is["J"], spec.pos_dim + 1),
+                                                    dtype=torch.float64, device=self.device)
         return self._hi
 
     def _enforce_all_rows(self, X_all, X, U, out):
@@ -202,8 +244,17 @@ class JacobiSCvx:
         idx = bad.nonzero().flatten()
         hi = self._hi_buffers()
         gidx = (idx + self.i0).to(torch.int32)
-        self.backend.collision_rows_indexed(X_all, gidx, c.R, c.j_max_hi, spec.pos_dim, c.cull_radius, hi["rows"],
-                                            hi["count"])
+        if self._is is None:
+            self.backend.collision_rows_indexed(X_all, gidx, c.R, c.j_max_hi, spec.pos_dim, c.cull_radius, hi["rows"],
+                                                hi["count"])
+        else:   # j_max_hi - 2J node rows, then the step's own continuous-time records of those agents
+            s = self._is
+            j_node = c.j_max_hi - 2 * s["J"]
+            self.backend.collision_rows_indexed(X_all, gidx, c.R, j_node, spec.pos_dim, c.cull_radius,
+                                                hi["rows_node"], hi["count"])
+            hi["rows"][:n_bad, :, :j_node].copy_(hi["rows_node"][:n_bad])
+            self.backend.append_collision_rows(X_all, self.i0, gidx, s["rec"], s["count_seg"], hi["rows"], hi["count"],
+                                               spec.pos_dim, s["overflow"])
         g = lambda t: t.index_select(0, idx).contiguous()  # noqa: E731
         o2 = hi["solver"].solve(g(self.disc), g(self.sigma), g(X), g(U), g(self.x_init), g(self.x_final), g(self.tr),
                                 hi["rows"][:n_bad], hi["count"][:n_bad], n=n_bad)
@@ -244,7 +295,8 @@ class JacobiSCvx:
     def step(self, X, U, marks=None):
         """One SCvx iteration; returns the new (X, U) and the raw solver outputs.
         marks: optional list; (stage, event) pairs are appended on the launch stream -- "start", then
-        the end of "foh", "gather" (all-gather), "rows" (collision rows), "qp" (the QP kernel),
+        the end of "foh", "gather" (all-gather), "rows" (collision rows), "isrows" (with CouplingSpec.intersample_S > 0: dense
+        roll-out, pair-rows scan and append), "qp" (the QP kernel),
         "check" (full-row check + re-solve) and "update" (bookkeeping); a stage's time is the
         difference to the previous mark."""
         torch = self.torch
@@ -260,9 +312,24 @@ class JacobiSCvx:
                 work.wait()
             X_all = self.X_all
             self._mark(marks, "gather")
-            rows, count = self.backend.collision_rows(X_all, self.i0, self.N, self.coupling.R, spec.j_max,
-                                                      spec.pos_dim, self.coupling.cull_radius, self.rows, self.count)
-            self._mark(marks, "rows")
+            if self._is is None:
+                rows, count = self.backend.collision_rows(X_all, self.i0, self.N, self.coupling.R, spec.j_max,
+                                                          spec.pos_dim, self.coupling.cull_radius, self.rows, self.count)
+                self._mark(marks, "rows")
+            else:
+                # the node rows take j_max - 2J slots of every node; the continuous-time rows of the current
+                # iterate (two per record: the segment's two nodes) follow them
+                s = self._is
+                self.backend.collision_rows(X_all, self.i0, self.N, self.coupling.R, s["j_node"], spec.pos_dim,
+                                            self.coupling.cull_radius, s["rows_node"], self.count)
+                self.rows[:, :, :s["j_node"]].copy_(s["rows_node"])
+                self._mark(marks, "rows")
+                s["rec"], s["count_seg"] = self.backend.intersample_pair_rows(
+                    spec.model, X, U, self.sigma, s["S"], self.nsub, spec.pos_dim, self.coupling.R, s["cull"], s["J"])
+                s["overflow"].zero_()
+                rows, count, _ = self.backend.append_collision_rows(X_all, self.i0, None, s["rec"], s["count_seg"],
+                                                                    self.rows, self.count, spec.pos_dim, s["overflow"])
+                self._mark(marks, "isrows")
         kw = {"order": self.order} if self.order is not None else {}
         out = self.solver.solve(self.disc, self.sigma, X, U, self.x_init, self.x_final, self.tr, rows, count,
                                 warm=self.warm, **kw)
@@ -275,6 +342,10 @@ class JacobiSCvx:
         self._mark(marks, "qp")
         if self.coupling is not None and self.coupling.check:
             out = self._enforce_all_rows(X_all, X, U, out)
+            if self._is is not None:
+                # continuous-time rows that did not fit a node's capacity, in this step's solve and re-solve (none
+                # by construction: the node rows leave 2J slots free)
+                self.last_check["is_overflow"] = int(self._is["overflow"].item())
             self._mark(marks, "check")
         # an agent whose subproblem failed numerically (status 2) rejects the step: it keeps its
         # iterate (its output may be non-finite and would otherwise reach every other agent through

@@ -28,7 +28,10 @@ extern "C" {
 #endif
 
 #define SCVX_HIP_VERSION 7   /* 7: fleet separation analysis (scvx_rollout_dense_batched, scvx_separation_scan_batched,
-                                  scvx_pair_min_distance_batched, scvx_obstacle_min_distance_batched) */
+                                  scvx_pair_min_distance_batched, scvx_obstacle_min_distance_batched); the
+                                  inter-sample collision rows (scvx_intersample_pair_rows_batched,
+                                  scvx_collision_rows_append_batched) were added to it without a bump: purely
+                                  additive, no existing argument list changed */
 
 #define SCVX_OK 0
 #define SCVX_EINVAL (-1)
@@ -514,6 +517,51 @@ int scvx_pair_min_distance_batched(int K, int n_x, int rows, int N, const double
  * r_o)); centers [n_obs][3], radii [n_obs] (device).  n_x >= 3. */
 int scvx_obstacle_min_distance_batched(int K, int n_x, int N, const double* X, int n_obs, const double* centers,
                                        const double* radii, double robot_radius, double* D, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Continuous-time (inter-sample) collision rows for the Jacobi QP (csrc/intersample_rows.hip):
+ * the pair scan above fed back into the subproblem.  Two entry points added to revision 7; no existing
+ * argument list changed.
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * Per local agent i in [i0, i0 + N_local) and segment k < K-1, the J neighbours that come closest strictly
+ * between the two nodes, on the samples P_all [N_total][K-1][S+1][3] / L_all [N_total][K-1] of
+ * scvx_rollout_dense_batched.  A pair's closest approach on the segment is the chord formula of
+ * scvx_separation_scan_batched over its own S sub-intervals (first minimum over s, replaced only when strictly
+ * smaller): (s, a), c = d0 + a e, dist = ||c||, alpha' = (s + a) / S.  The pair is a candidate when
+ *     dist < cull,   0 < alpha' < 1 (a minimum at a node belongs to the node rows),   dist > 0
+ * (coincident chords have no direction and are dropped; the comparisons are made on dist^2 against cull^2).
+ * The J candidates of smallest dist are kept, ties to the lower j, and written in ascending (dist, j) order:
+ *     rec   [N_local][K-1][J][4]   g = c / dist (3 doubles, zeros past pos_dim as P_all), v = 2R - dist
+ *     nbr   [N_local][K-1][J]      int32 j            alpha [N_local][K-1][J]   alpha'
+ *     count [N_local][K-1]         int32 records kept; slots past it hold zeros, nbr -1
+ * The output does not depend on the launch geometry: a shard (i0, N_local) returns the matching rows of the full
+ * launch bit for bit.  flags: 0; bit 0 (tests only) disables the skip of neighbours with
+ * ||d(s=0)|| - (L_i + L_j) >= cull (1 + 1e-12), which cannot be candidates -- bit-identical outputs either way.
+ * Limits: K <= 64, 1 <= S <= 16, 1 <= J <= 8, cull > 0.
+ */
+int scvx_intersample_pair_rows_batched(int K, int S, int N_total, const double* P_all, const double* L_all, int i0,
+                                       int N_local, double R, double cull, int J, double* rec, int32_t* nbr,
+                                       double* alpha, int32_t* count, int flags, void* stream);
+
+/*
+ * Append those records to the node rows of scvx_collision_rows_batched / _indexed.  A record of segment k becomes
+ * two node rows, at node k and at node k+1, each g'(p_t - pbar_t) >= v - S_t, i.e. in the QP's form
+ * b - g' p_t <= S_t with b = v + g' pbar_t, pbar_t = X_all[i][t][0:pos_dim] (summed left to right, unfused).
+ * Shifting both end nodes along g by the deficit shifts every point of the node chord by as much, so the
+ * first-order image of the closest point clears 2R.  For local agent a and node t < K-1, behind the count[a][t]
+ * rows already present: segment t's records first, then segment t-1's.  No row at node K-1.  Never writes past
+ * j_max rows per node; *overflow (one device int32, accumulated, zeroed by the caller) counts the rows that did
+ * not fit.  idx NULL: local agent a is global agent i0 + a and reads rec / count_seg [a].  idx (device int32
+ * [N_local], as scvx_collision_rows_indexed): local agent a is global agent idx[a] and reads rec / count_seg
+ * [idx[a] - i0], which the caller guarantees to lie inside those buffers.
+ *   rows [N_local][K][j_max][pos_dim+1], count [N_local][K] (in / out), rec [.][K-1][J][4], count_seg [.][K-1].
+ */
+int scvx_collision_rows_append_batched(int K, int pos_dim, int n_x, int N_total, const double* X_all, int i0,
+                                       const int32_t* idx, int N_local, int J, const double* rec,
+                                       const int32_t* count_seg, int j_max, double* rows, int32_t* count,
+                                       int32_t* overflow, void* stream);
 
 #ifdef __cplusplus
 }
