@@ -5,37 +5,31 @@
 //                                  between the two nodes, as records (g, v, j, alpha')       (the hot path)
 //   collision_rows_append_kernel   each record becomes two node rows, behind the node rows of collision.hip
 //
-// A pair's closest approach on segment k is that of separation_scan_kernel: the S chords of the relative
-// position between consecutive samples at equal normalised time, the first minimum over s (replaced only when
-// strictly smaller), c = d0 + a e its relative position, dist = |c|, alpha' = (s + a) / S.  The pair is a
+// Mapping, tile staging and the chords of a pair are csrc/pair_scan.hpp's, the ones separation_scan_kernel runs.  A
+// pair's closest approach on segment k is the first minimum over its S chords (replaced only when strictly
+// smaller): c its relative position there, dist = |c|, alpha' = (s + a) / S.  The pair is a
 // candidate when dist < cull, 0 < alpha' < 1 (a minimum at a node belongs to the node rows) and dist > 0 (no
 // direction otherwise: dropped).  Per (i, k) the J candidates of smallest dist are kept in ascending (dist, j)
 // order -- neighbours are scanned j ascending and a candidate moves ahead of a kept one only when strictly
 // closer -- so the output does not depend on the launch geometry.  Record: g = c / dist, v = 2R - dist.
 //
-// Mapping: separation_scan_kernel's.  One workgroup of 64 lanes per (segment, block of 64 local agents), lane =
-// local agent, own samples in registers, tiles of SEP_TJ neighbours staged in LDS and read as broadcasts.  Each
-// lane keeps its sorted top-J list (dist^2, j, s, a) in registers; the insertion runs under a wave ballot with
-// the running bound "the J-th kept dist^2" (as collision_rows_kernel); c is recomputed once at the end with the
-// scan's own expressions, so dist^2 comes out bit for bit as selected.
+// Each lane keeps its sorted top-J list (dist^2, j, s, a) in registers; the insertion runs under a wave ballot with
+// the running bound "the J-th kept dist^2" (as collision_rows_kernel); c is recomputed once at the end by
+// approach_point, the statement the chords use, so dist^2 comes out bit for bit as selected.
 //
-// Chunk skip: the relative position of a pair stays within L_i + L_j of d(s=0), so a neighbour with
-// |d(s=0)| - (L_i + L_j) >= cull (1 + 1e-12) is no candidate.  The threshold is fixed (the scan's moves with the
-// kept minimum): each lane tests the neighbours of a tile once, into a bit mask, a chunk is skipped when a wave
-// ballot finds no lane needing any of its neighbours, and the outputs are bit-identical to the unpruned kernel
-// (flags bit 0, tests only).
+// Chunk skip: a neighbour whose bound |d(s=0)| - (L_i + L_j) is cull (1 + PS_SKIP_MARGIN) or more is no candidate.
+// The threshold is fixed (the scan's moves with the kept minimum): each lane tests the neighbours of a tile once,
+// into a bit mask, a chunk is skipped when a wave ballot finds no lane needing any of its neighbours, and the
+// outputs are bit-identical to the unpruned kernel (flags bit 0, tests only).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "common.hpp"
+#include "pair_scan.hpp"
 #include "scvx_hip.h"
 
 namespace scvx {
-
-constexpr int ISR_TJ = 32;  // neighbours staged per LDS tile (separation.hip's SEP_TJ)
-constexpr int ISR_CH = 4;   // neighbours per chunk of the skip test
-constexpr double ISR_SKIP_MARGIN = 1e-12;
 
 template <int S, int JM, bool PRUNE>
 __global__ __launch_bounds__(64) void intersample_pair_rows_kernel(int K, int N_total, int N_local,
@@ -45,16 +39,15 @@ __global__ __launch_bounds__(64) void intersample_pair_rows_kernel(int K, int N_
                                                                    double* __restrict__ rec, int32_t* __restrict__ nbr,
                                                                    double* __restrict__ alpha,
                                                                    int32_t* __restrict__ count) {
-    constexpr int W = (S + 1) * 3;  // doubles per (agent, segment)
-    __shared__ double tile[ISR_TJ * W];
-    __shared__ double tileL[ISR_TJ];
+    constexpr int W = (S + 1) * 3;
+    __shared__ double tile[PS_TJ * W];
+    __shared__ double tileL[PS_TJ];
     const int lane = threadIdx.x;
     const int k = blockIdx.y;  // segment, < K-1
     const long long a = (long long)blockIdx.x * 64 + lane;
     const bool live = a < N_local;
     const long long gi = live ? i0 + a : -1;
-    double pi[W];
-    double Li = 0.0;
+    double pi[W], Li = 0.0;
 #pragma unroll
     for (int e = 0; e < W; ++e) pi[e] = live ? P_all[(gi * (K - 1) + k) * W + e] : 0.0;
     if (PRUNE && live) Li = L_all[gi * (K - 1) + k];
@@ -65,53 +58,41 @@ __global__ __launch_bounds__(64) void intersample_pair_rows_kernel(int K, int N_
     for (int r = 0; r < JM; ++r) { kq[r] = INFINITY; ka[r] = 0.0; kj[r] = -1; ks[r] = 0; }
     const double cull2 = cull * cull;
     double bound = cull2;  // a candidate enters only below min(cull^2, the J-th kept dist^2)
-    for (int j0 = 0; j0 < N_total; j0 += ISR_TJ) {
-        const int nt = min(ISR_TJ, N_total - j0);
-        __syncthreads();
-        // the tile is a whole number of chunks; slots past nt hold zeros and are never selected (j < N_total below)
-        for (int e = lane; e < ISR_TJ * W; e += 64) {
-            const int jj = e / W;
-            tile[e] = jj < nt ? P_all[((long long)(j0 + jj) * (K - 1) + k) * W + (e - jj * W)] : 0.0;
-        }
-        if (PRUNE && lane < ISR_TJ) tileL[lane] = lane < nt ? L_all[(long long)(j0 + lane) * (K - 1) + k] : 0.0;
-        __syncthreads();
+    for (int j0 = 0; j0 < N_total; j0 += PS_TJ) {
+        const int nt = stage_tile<S, PRUNE>(tile, tileL, P_all, L_all, j0, N_total, K, k, lane);
         // the skip test of the whole tile at once, one bit per neighbour: 32 independent chains whose LDS reads
         // overlap (made chunk by chunk, each test waited for its own reads with nothing else to issue)
         uint32_t needmask = 0;
         if (PRUNE) {
 #pragma unroll
-            for (int jj = 0; jj < ISR_TJ; ++jj) {
+            for (int jj = 0; jj < PS_TJ; ++jj) {
                 const double* pj = tile + jj * W;
                 const double x0 = pi[0] - pj[0], x1 = pi[1] - pj[1], x2 = pi[2] - pj[2];
-                const double r = (cull + Li + tileL[jj]) * (1.0 + ISR_SKIP_MARGIN);
-                needmask |= (fma(x2, x2, fma(x1, x1, x0 * x0)) >= r * r) ? 0u : (1u << jj);
+                const double r = (cull + Li + tileL[jj]) * (1.0 + PS_SKIP_MARGIN);
+                needmask |= (sq3(x0, x1, x2) >= r * r) ? 0u : (1u << jj);
             }
             needmask = live ? needmask : 0u;
         }
-        for (int jb = 0; jb < nt; jb += ISR_CH) {
-            if (PRUNE && !__builtin_amdgcn_ballot_w64(((needmask >> jb) & ((1u << ISR_CH) - 1u)) != 0u)) continue;
+        for (int jb = 0; jb < nt; jb += PS_CH) {
+            if (PRUNE && !__builtin_amdgcn_ballot_w64(((needmask >> jb) & ((1u << PS_CH) - 1u)) != 0u)) continue;
 #pragma unroll 1
-            for (int c = 0; c < ISR_CH; ++c) {
-                const double* pj = tile + (jb + c) * W;
+            for (int c = 0; c < PS_CH; ++c) {
                 const int j = j0 + jb + c;
                 const bool ok = live && j < N_total && j != gi;
-                // the pair's own first minimum over its S chords (separation_scan_kernel's expressions)
+                // the pair's own first minimum over its S chords
                 double bq = INFINITY, ba = 0.0;
                 int bs = 0;
-                double d0[3] = {pi[0] - pj[0], pi[1] - pj[1], pi[2] - pj[2]};
+                const double* pj = tile + (jb + c) * W;
+                double d0[3];
+                rel_pos(pi, pj, 0, d0);
 #pragma unroll
                 for (int s = 0; s < S; ++s) {
-                    const double d1[3] = {pi[(s + 1) * 3] - pj[(s + 1) * 3], pi[(s + 1) * 3 + 1] - pj[(s + 1) * 3 + 1],
-                                          pi[(s + 1) * 3 + 2] - pj[(s + 1) * 3 + 2]};
-                    const double e0 = d1[0] - d0[0], e1 = d1[1] - d0[1], e2 = d1[2] - d0[2];
-                    const double ee = fma(e2, e2, fma(e1, e1, e0 * e0));
-                    const double de = fma(d0[2], e2, fma(d0[1], e1, d0[0] * e0));
-                    const double al = ee == 0.0 ? 0.0 : fmin(fmax(-de / ee, 0.0), 1.0);
-                    const double c0 = fma(al, e0, d0[0]), c1 = fma(al, e1, d0[1]), c2 = fma(al, e2, d0[2]);
-                    const double q = fma(c2, c2, fma(c1, c1, c0 * c0));
-                    const bool take = q < bq;
-                    bq = take ? q : bq;
-                    ba = take ? al : ba;
+                    double d1[3];
+                    rel_pos(pi, pj, s + 1, d1);
+                    const Approach m = chord_closest(d0, d1);
+                    const bool take = m.q < bq;
+                    bq = take ? m.q : bq;
+                    ba = take ? m.al : ba;
                     bs = take ? s : bs;
                     d0[0] = d1[0]; d0[1] = d1[1]; d0[2] = d1[2];
                 }
@@ -156,16 +137,13 @@ __global__ __launch_bounds__(64) void intersample_pair_rows_kernel(int K, int N_
         ++n;
         const int s = ks[r];
         const double al = ka[r];
-        const double* qi = P_all + (gi * (K - 1) + k) * W + s * 3;
-        const double* qj = P_all + ((long long)kj[r] * (K - 1) + k) * W + s * 3;
-        const double d0[3] = {qi[0] - qj[0], qi[1] - qj[1], qi[2] - qj[2]};
-        const double d1[3] = {qi[3] - qj[3], qi[4] - qj[4], qi[5] - qj[5]};
-        const double e0 = d1[0] - d0[0], e1 = d1[1] - d0[1], e2 = d1[2] - d0[2];
-        const double c0 = fma(al, e0, d0[0]), c1 = fma(al, e1, d0[1]), c2 = fma(al, e2, d0[2]);
-        const double dist = sqrt(fma(c2, c2, fma(c1, c1, c0 * c0)));
-        out[0] = c0 / dist;
-        out[1] = c1 / dist;
-        out[2] = c2 / dist;
+        double cp[3];
+        approach_point(P_all + (gi * (K - 1) + k) * W + s * 3,
+                       P_all + ((long long)kj[r] * (K - 1) + k) * W + s * 3, al, cp);
+        const double dist = sqrt(sq3(cp[0], cp[1], cp[2]));
+        out[0] = cp[0] / dist;
+        out[1] = cp[1] / dist;
+        out[2] = cp[2] / dist;
         out[3] = 2.0 * R - dist;
         nbr[o * J + r] = kj[r];
         alpha[o * J + r] = ((double)s + al) / (double)S;
@@ -247,21 +225,14 @@ extern "C" int scvx_intersample_pair_rows_batched(int K, int S, int N_total, con
                                                   int i0, int N_local, double R, double cull, int J, double* rec,
                                                   int32_t* nbr, double* alpha, int32_t* count, int flags,
                                                   void* stream) {
-    if (K < 2 || K > 64 || S < 1 || S > 16 || N_total < 0 || N_local < 0 || i0 < 0 ||
-        i0 + (long long)N_local > N_total || J < 1 || J > 8 || !(cull > 0.0) || !(R == R) || (flags & ~1) || !P_all ||
-        !L_all || !rec || !nbr || !alpha || !count)
+    if (!pair_scan_args_ok(K, 64, S, N_total, N_local, i0, flags, P_all, L_all) || J < 1 || J > 8 || !(cull > 0.0) ||
+        !(R == R) || !rec || !nbr || !alpha || !count)
         return set_error(SCVX_EINVAL, "intersample_pair_rows: bad args");
     if (N_local == 0) return SCVX_OK;
-    hipStream_t st = (hipStream_t)stream;
-    switch (S) {
-#define SCVX_ISR(s)                                                                                                \
-    case s:                                                                                                        \
-        return launch_pair_rows<s>(K, N_total, P_all, L_all, i0, N_local, R, cull, J, rec, nbr, alpha, count, flags, st);
-        SCVX_ISR(1) SCVX_ISR(2) SCVX_ISR(3) SCVX_ISR(4) SCVX_ISR(5) SCVX_ISR(6) SCVX_ISR(7) SCVX_ISR(8)
-        SCVX_ISR(9) SCVX_ISR(10) SCVX_ISR(11) SCVX_ISR(12) SCVX_ISR(13) SCVX_ISR(14) SCVX_ISR(15) SCVX_ISR(16)
-#undef SCVX_ISR
-    }
-    return set_error(SCVX_EINVAL, "intersample_pair_rows: bad args");
+    return dispatch_S(S, "intersample_pair_rows", [&](auto tag) {
+        return launch_pair_rows<decltype(tag)::S>(K, N_total, P_all, L_all, i0, N_local, R, cull, J, rec, nbr, alpha,
+                                                  count, flags, (hipStream_t)stream);
+    });
 }
 
 extern "C" int scvx_collision_rows_append_batched(int K, int pos_dim, int n_x, int N_total, const double* X_all, int i0,

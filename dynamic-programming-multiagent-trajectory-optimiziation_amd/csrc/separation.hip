@@ -6,42 +6,29 @@
 //   pair_min_kernel           node-level pairwise minimum distance, SCvx/utils/analysis.py:10-31
 //   obstacle_min_kernel       node-level agent-obstacle clearance, SCvx/utils/analysis.py:34-62
 //
-// The scan compares agents at EQUAL normalised time: sample s of segment k of every agent sits at
-// tau = (k + s/S) / (K-1) of its own horizon, the pairing the node-level collision rows use (collision.hip).
-// Between two consecutive samples both agents move on chords, so the relative position is d0 + a (d1 - d0),
-// a in [0, 1], and its closest approach to the origin is the clamped projection below: exact for the
-// piecewise-linear interpolant of the samples, within max ||r''|| h^2 / 8 of the true minimum (h = the
-// sub-interval, r the relative position).
+// The scan's mapping, tile staging and chord closest approach are csrc/pair_scan.hpp's, shared with the collision rows
+// (intersample_rows.hip); its accuracy: within max ||r''|| h^2 / 8 of the true minimum (h = the sub-interval, r the
+// relative position).  Here: the selection and the skip rule.
 //
-// Scan mapping (as collision_rows_kernel): one workgroup per (segment k, block of 64 local agents), lane =
-// local agent.  The lane's own S+1 samples stay in registers; all lanes walk the same neighbour sequence
-// j = 0..N_total-1, so the (S+1) x 3 samples of a tile of SEP_TJ neighbours are staged in LDS once per
-// workgroup and read back as broadcasts.  Neighbours are processed in branch-free chunks of SEP_CH; the
-// selection keeps squared distances (one sqrt at the end) and replaces only on strictly smaller, in the
-// order j ascending, s ascending: the first minimum, whatever the launch geometry.
+// Selection: squared distances (one sqrt at the end), replaced only on strictly smaller, in the order j ascending,
+// s ascending: the first minimum, whatever the launch geometry.
 //
-// Chunk skip: a pair's relative position stays within L_i + L_j (the polyline lengths of the two segments)
-// of d(s=0), so no chord of it comes closer than |d(s=0)| - (L_i + L_j).  When that bound, held back by
-// SEP_SKIP_MARGIN, exceeds the lane's current minimum (or the sample-0 distance to a block mate, which the
-// final minimum cannot exceed) for every neighbour of a chunk in every lane (wave ballot), the chunk is
-// skipped: none of its candidates could have been the first minimum, so the outputs are bit-identical to the
-// unpruned scan (flags bit 0 selects it, for the test of exactly that).  Measured 4.4x faster at the C4 shape and
-// 1.7x at C3.
+// Chunk skip: when the bound |d(s=0)| - (L_i + L_j), held back by PS_SKIP_MARGIN, exceeds the lane's current
+// minimum (or the sample-0 distance to a block mate, which the final minimum cannot exceed) for every neighbour of a
+// chunk in every lane (wave ballot), the chunk is skipped: none of its candidates could have been the first minimum, so
+// the outputs are bit-identical to the unpruned scan (flags bit 0 selects it, for the test of exactly that).  Measured
+// 4.4x faster at the C4 shape and 1.7x at C3.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 
 #include "common.hpp"
 #include "models.hpp"
+#include "pair_scan.hpp"
 #include "scvx_hip.h"
 
 namespace scvx {
-
-constexpr int SEP_TJ = 32;  // neighbours staged per LDS tile: 32 x 51 doubles = 12.75 KiB at S = 16
-constexpr int SEP_CH = 4;   // neighbours per branch-free chunk
-// the skip compares rounded quantities: d(s=0), L and sqrt(min) each carry a few ulp (1e-16 relative to the
-// pair's distance), the margin is four orders of magnitude above that
-constexpr double SEP_SKIP_MARGIN = 1e-12;
 
 // one lane per (agent, segment): restart at X[:,k], FOH input u_k + tau/T (u_{k+1} - u_k), T = sigma/(K-1)
 // (nonlinear_body's piecewise roll-out, foh_body.hpp), sampled every `sub` RK4 steps (rk4_step)
@@ -91,16 +78,15 @@ __global__ __launch_bounds__(64) void separation_scan_kernel(int K, int N_total,
                                                              const double* __restrict__ L_all, int i0,
                                                              double* __restrict__ sep, int32_t* __restrict__ arg,
                                                              double* __restrict__ alpha) {
-    constexpr int W = (S + 1) * 3;  // doubles per (agent, segment)
-    __shared__ double tile[SEP_TJ * W];
-    __shared__ double tileL[SEP_TJ];
+    constexpr int W = (S + 1) * 3;
+    __shared__ double tile[PS_TJ * W];
+    __shared__ double tileL[PS_TJ];
     const int lane = threadIdx.x;
     const int k = blockIdx.y;  // segment, < K-1
     const long long a = (long long)blockIdx.x * 64 + lane;
     const bool live = a < N_local;
     const long long gi = live ? i0 + a : -1;
-    double pi[W];
-    double Li = 0.0;
+    double pi[W], Li = 0.0;
 #pragma unroll
     for (int e = 0; e < W; ++e) pi[e] = live ? P_all[(gi * (K - 1) + k) * W + e] : 0.0;
     if (PRUNE && live) Li = L_all[gi * (K - 1) + k];
@@ -117,20 +103,12 @@ __global__ __launch_bounds__(64) void separation_scan_kernel(int K, int N_total,
         const int nb = (int)min(64LL, N_local - (long long)blockIdx.x * 64);
         for (int l = 0; l < nb; ++l) {
             const double x0 = pi[0] - blk[l * 3], x1 = pi[1] - blk[l * 3 + 1], x2 = pi[2] - blk[l * 3 + 2];
-            ub = l == lane ? ub : fmin(ub, fma(x2, x2, fma(x1, x1, x0 * x0)));
+            ub = l == lane ? ub : fmin(ub, sq3(x0, x1, x2));
         }
     }
-    for (int j0 = 0; j0 < N_total; j0 += SEP_TJ) {
-        const int nt = min(SEP_TJ, N_total - j0);
-        __syncthreads();
-        // the tile is a whole number of chunks; slots past nt hold zeros and are never selected (j < N_total below)
-        for (int e = lane; e < SEP_TJ * W; e += 64) {
-            const int jj = e / W;
-            tile[e] = jj < nt ? P_all[((long long)(j0 + jj) * (K - 1) + k) * W + (e - jj * W)] : 0.0;
-        }
-        if (PRUNE && lane < SEP_TJ) tileL[lane] = lane < nt ? L_all[(long long)(j0 + lane) * (K - 1) + k] : 0.0;
-        __syncthreads();
-        for (int jb = 0; jb < nt; jb += SEP_CH) {
+    for (int j0 = 0; j0 < N_total; j0 += PS_TJ) {
+        const int nt = stage_tile<S, PRUNE>(tile, tileL, P_all, L_all, j0, N_total, K, k, lane);
+        for (int jb = 0; jb < nt; jb += PS_CH) {
             if (PRUNE) {
                 // d(s=0)^2 > ((sqrt(min(best, ub)) + L_i + L_j) (1 + margin))^2: every chord of the pair is longer
                 // than the kept minimum or than the block mate's that will replace it (strictly: a coincident
@@ -138,35 +116,31 @@ __global__ __launch_bounds__(64) void separation_scan_kernel(int K, int N_total,
                 const double sb = sqrt(fmin(best, ub));
                 bool need = false;
 #pragma unroll
-                for (int c = 0; c < SEP_CH; ++c) {
+                for (int c = 0; c < PS_CH; ++c) {
                     const double* pj = tile + (jb + c) * W;
                     const double x0 = pi[0] - pj[0], x1 = pi[1] - pj[1], x2 = pi[2] - pj[2];
-                    const double r = (sb + Li + tileL[jb + c]) * (1.0 + SEP_SKIP_MARGIN);
-                    need |= !(fma(x2, x2, fma(x1, x1, x0 * x0)) > r * r);
+                    const double r = (sb + Li + tileL[jb + c]) * (1.0 + PS_SKIP_MARGIN);
+                    need |= !(sq3(x0, x1, x2) > r * r);
                 }
                 if (!__builtin_amdgcn_ballot_w64(need && live)) continue;
             }
             // one neighbour at a time: its S sub-intervals are independent work enough, and unrolling the chunk as
-            // well would hold SEP_CH sets of samples in registers next to the lane's own (spills at S >= 8)
+            // well would hold PS_CH sets of samples in registers next to the lane's own (spills at S >= 8)
 #pragma unroll 1
-            for (int c = 0; c < SEP_CH; ++c) {
-                const double* pj = tile + (jb + c) * W;
+            for (int c = 0; c < PS_CH; ++c) {
                 const int j = j0 + jb + c;
                 const bool ok = live && j < N_total && j != gi;
-                double d0[3] = {pi[0] - pj[0], pi[1] - pj[1], pi[2] - pj[2]};
+                const double* pj = tile + (jb + c) * W;
+                double d0[3];
+                rel_pos(pi, pj, 0, d0);
 #pragma unroll
                 for (int s = 0; s < S; ++s) {
-                    const double d1[3] = {pi[(s + 1) * 3] - pj[(s + 1) * 3], pi[(s + 1) * 3 + 1] - pj[(s + 1) * 3 + 1],
-                                          pi[(s + 1) * 3 + 2] - pj[(s + 1) * 3 + 2]};
-                    const double e0 = d1[0] - d0[0], e1 = d1[1] - d0[1], e2 = d1[2] - d0[2];
-                    const double ee = fma(e2, e2, fma(e1, e1, e0 * e0));
-                    const double de = fma(d0[2], e2, fma(d0[1], e1, d0[0] * e0));
-                    const double al = ee == 0.0 ? 0.0 : fmin(fmax(-de / ee, 0.0), 1.0);
-                    const double c0 = fma(al, e0, d0[0]), c1 = fma(al, e1, d0[1]), c2 = fma(al, e2, d0[2]);
-                    const double q = fma(c2, c2, fma(c1, c1, c0 * c0));
-                    const bool take = ok && q < best;
-                    best = take ? q : best;
-                    balpha = take ? al : balpha;
+                    double d1[3];
+                    rel_pos(pi, pj, s + 1, d1);
+                    const Approach m = chord_closest(d0, d1);
+                    const bool take = ok && m.q < best;
+                    best = take ? m.q : best;
+                    balpha = take ? m.al : balpha;
                     bj = take ? j : bj;
                     bs = take ? s : bs;
                     d0[0] = d1[0]; d0[1] = d1[1]; d0[2] = d1[2];
@@ -298,18 +272,13 @@ extern "C" int scvx_rollout_dense_batched(int model_id, const double* params, in
 extern "C" int scvx_separation_scan_batched(int K, int S, int N_total, const double* P_all, const double* L_all, int i0,
                                             int N_local, double* sep, int32_t* arg, double* alpha, int flags,
                                             void* stream) {
-    if (K < 2 || S < 1 || S > 16 || N_total < 0 || N_local < 0 || i0 < 0 || i0 + (long long)N_local > N_total ||
-        (flags & ~1) || !P_all || !L_all || !sep || !arg || !alpha)
+    if (!pair_scan_args_ok(K, INT_MAX, S, N_total, N_local, i0, flags, P_all, L_all) || !sep || !arg || !alpha)
         return set_error(SCVX_EINVAL, "separation_scan: bad args");
     if (N_local == 0) return SCVX_OK;
-    hipStream_t st = (hipStream_t)stream;
-    switch (S) {
-#define SCVX_SCAN(s) case s: return launch_scan<s>(K, N_total, P_all, L_all, i0, N_local, sep, arg, alpha, flags, st);
-        SCVX_SCAN(1) SCVX_SCAN(2) SCVX_SCAN(3) SCVX_SCAN(4) SCVX_SCAN(5) SCVX_SCAN(6) SCVX_SCAN(7) SCVX_SCAN(8)
-        SCVX_SCAN(9) SCVX_SCAN(10) SCVX_SCAN(11) SCVX_SCAN(12) SCVX_SCAN(13) SCVX_SCAN(14) SCVX_SCAN(15) SCVX_SCAN(16)
-#undef SCVX_SCAN
-    }
-    return set_error(SCVX_EINVAL, "separation_scan: bad args");
+    return dispatch_S(S, "separation_scan", [&](auto tag) {
+        return launch_scan<decltype(tag)::S>(K, N_total, P_all, L_all, i0, N_local, sep, arg, alpha, flags,
+                                             (hipStream_t)stream);
+    });
 }
 
 extern "C" int scvx_pair_min_distance_batched(int K, int n_x, int rows, int N, const double* X, double* D,

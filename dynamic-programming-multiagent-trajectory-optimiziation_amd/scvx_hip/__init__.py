@@ -748,6 +748,20 @@ def rollout_dense(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=None,
     return P, L
 
 
+def _check_samples(who, P_all, L_all, i0, n_local, k_max=None):
+    """The dense-sample arguments of the pair-scan entry points -> (N_total, K-1, S, i0, n_local); k_max: the
+    entry point's upper bound on K, if it has one."""
+    if P_all.dim() != 4 or P_all.shape[3] != 3 or P_all.shape[2] < 2 or tuple(L_all.shape) != tuple(P_all.shape[:2]):
+        raise ValueError(f"{who}: P_all (N_total,K-1,S+1,3) and L_all (N_total,K-1) expected")
+    N_total, Km1, S = P_all.shape[0], P_all.shape[1], P_all.shape[2] - 1
+    i0, n_local = int(i0), int(n_local)
+    if S > 16 or Km1 < 1 or (k_max and Km1 >= k_max) or i0 < 0 or n_local < 0 or i0 + n_local > N_total:
+        raise ValueError(f"{who}: S <= 16, {f'2 <= K <= {k_max}' if k_max else 'K >= 2'} and 0 <= i0, "
+                         f"i0 + n_local <= N_total required; got S={S}, K-1={Km1}, i0={i0}, n_local={n_local}, "
+                         f"N_total={N_total}")
+    return N_total, Km1, S, i0, n_local
+
+
 def separation_scan(P_all, L_all, i0, n_local, stream=None, prune=True):
     """Continuous-time closest approach of local agents [i0, i0+n_local) to every other agent of P_all
     (N_total,K-1,S+1,3) / L_all (N_total,K-1) (rollout_dense's outputs) at equal normalised time
@@ -758,13 +772,7 @@ def separation_scan(P_all, L_all, i0, n_local, stream=None, prune=True):
     max ||r''|| h^2 / 8 of the continuous minimum, h = 1 / ((K-1) S) in normalised time, r the relative position.
     prune=False (tests) disables the skip of far neighbours; the outputs are bit-identical."""
     torch = _torch()
-    if P_all.dim() != 4 or P_all.shape[3] != 3 or P_all.shape[2] < 2 or tuple(L_all.shape) != tuple(P_all.shape[:2]):
-        raise ValueError("separation_scan: P_all (N_total,K-1,S+1,3) and L_all (N_total,K-1) expected")
-    N_total, Km1, S = P_all.shape[0], P_all.shape[1], P_all.shape[2] - 1
-    i0, n_local = int(i0), int(n_local)
-    if S > 16 or Km1 < 1 or i0 < 0 or n_local < 0 or i0 + n_local > N_total:
-        raise ValueError(f"separation_scan: S <= 16, K >= 2 and 0 <= i0, i0 + n_local <= N_total required; got S={S}, "
-                         f"K-1={Km1}, i0={i0}, n_local={n_local}, N_total={N_total}")
+    N_total, Km1, S, i0, n_local = _check_samples("separation_scan", P_all, L_all, i0, n_local)
     dev = P_all.device
     sep = torch.empty((n_local, Km1), dtype=torch.float64, device=dev)
     arg = torch.empty((n_local, Km1, 2), dtype=torch.int32, device=dev)
@@ -803,13 +811,8 @@ def intersample_pair_rows(P_all, L_all, i0, n_local, R, cull, J=2, stream=None, 
     v = 2R - dist, nbr (n_local,K-1,J) int32 the neighbour (-1 past count), alpha (n_local,K-1,J) = alpha' and count
     (n_local,K-1) int32.  prune=False (tests) disables the skip of far neighbours; the outputs are bit-identical."""
     torch = _torch()
-    if P_all.dim() != 4 or P_all.shape[3] != 3 or P_all.shape[2] < 2 or tuple(L_all.shape) != tuple(P_all.shape[:2]):
-        raise ValueError("intersample_pair_rows: P_all (N_total,K-1,S+1,3) and L_all (N_total,K-1) expected")
-    N_total, Km1, S = P_all.shape[0], P_all.shape[1], P_all.shape[2] - 1
-    i0, n_local, J = int(i0), int(n_local), int(J)
-    if S > 16 or not 1 <= Km1 <= 63 or i0 < 0 or n_local < 0 or i0 + n_local > N_total:
-        raise ValueError(f"intersample_pair_rows: S <= 16, 2 <= K <= 64 and 0 <= i0, i0 + n_local <= N_total required; "
-                         f"got S={S}, K-1={Km1}, i0={i0}, n_local={n_local}, N_total={N_total}")
+    N_total, Km1, S, i0, n_local = _check_samples("intersample_pair_rows", P_all, L_all, i0, n_local, k_max=64)
+    J = int(J)
     if not 1 <= J <= 8 or not float(cull) > 0.0:
         raise ValueError(f"intersample_pair_rows: 1 <= J <= 8 and cull > 0 required, got J={J}, cull={cull}")
     dev = P_all.device
