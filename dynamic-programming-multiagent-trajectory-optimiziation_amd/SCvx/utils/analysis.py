@@ -6,7 +6,9 @@ obstacle minima run in scvx_pair_min_distance_batched / scvx_obstacle_min_distan
 reference's Python double loop; the dense roll-outs in scvx_rollout_dense_batched.
 
 Added here (no reference counterpart): `min_inter_agent_separation_continuous`, the closest approach of
-any two agents BETWEEN the nodes as well as at them (scvx_hip.fleet_separation).
+any two agents BETWEEN the nodes as well as at them (scvx_hip.fleet_separation), and
+`min_agent_obstacle_clearance_continuous`, the same for agents against obstacles
+(scvx_hip.fleet_obstacle_clearance).
 """
 from typing import List, Sequence, Tuple
 
@@ -89,6 +91,45 @@ def compute_intersample_clearance(X: np.ndarray, U: np.ndarray, foh, obs_center:
     tau_disc = np.arange(K)
     h_disc = np.linalg.norm(X[:pd].T - c.reshape(1, pd), axis=1) - total_radius
     return tau_cont, h_cont, tau_disc, h_disc
+
+
+def _device_model(foh_or_model, who, device):
+    """(built-in model name, params, device) of a FirstOrderHold, a model object or a built-in device model name."""
+    if isinstance(foh_or_model, FirstOrderHold):
+        return (builtin_model(foh_or_model.model, who), getattr(foh_or_model.model, "scvx_params", None),
+                getattr(foh_or_model, "_device", device))
+    if isinstance(foh_or_model, str):
+        return foh_or_model, None, device
+    return builtin_model(foh_or_model, who), getattr(foh_or_model, "scvx_params", None), device
+
+
+def min_agent_obstacle_clearance_continuous(X_list: List[np.ndarray], U_list: List[np.ndarray], foh_or_model, sigma,
+                                            obstacles: Sequence, robot_radius: float, S: int = 8,
+                                            device="cuda") -> Tuple[float, np.ndarray]:
+    """min_agent_obstacle_distance in continuous time (not in the reference): (d_min_global, d_mat) with
+    d_mat[i, j] = min over the whole trajectory, between the nodes as well as at them, of
+    ||p_i - c_j|| - (robot_radius + r_j); d_min_global its minimum (negative when penetrating).
+
+    X_list / U_list: per agent (n, K) / (m, K); foh_or_model: a FirstOrderHold, a model object or a built-in
+    device model name; sigma: one horizon for all agents or one per agent; obstacles [(centre, radius)], centres
+    of up to 3 coordinates.
+
+    Accuracy: exact for the piecewise-linear interpolant of S samples per segment; within max ||r''|| h^2 / 8 of
+    the continuous minimum, h = 1 / ((K-1) S) in normalised time and r = p - c (double integrator:
+    ||r''|| <= max(sigma^2 ||u||)).  Never above min_agent_obstacle_distance's matrix: the nodes are samples."""
+    import torch
+    who = "min_agent_obstacle_clearance_continuous"
+    model, params, device = _device_model(foh_or_model, who, device)
+    N = len(X_list)
+    if len(U_list) != N:
+        raise ValueError(f"{who}: X_list and U_list must have the same length")
+    sig = np.broadcast_to(np.asarray(sigma, float), (N,)).copy()
+    K = np.asarray(X_list[0]).shape[1]
+    nsub = max(16, scvx_hip.default_nsub(model, float(sig.max()), K)) if model not in ("di", "si") else None
+    out = scvx_hip.fleet_obstacle_clearance(model, _stack(X_list, device), _stack(U_list, device),
+                                            torch.as_tensor(sig, device=device), list(obstacles), robot_radius, S=S,
+                                            nsub=nsub, params=params)
+    return out["min"], out["D"].cpu().numpy()
 
 
 def min_inter_agent_separation_continuous(X_list: List[np.ndarray], U_list: List[np.ndarray], foh_or_model, sigma,

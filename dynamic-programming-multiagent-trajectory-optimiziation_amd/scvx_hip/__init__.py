@@ -16,6 +16,8 @@ kernels run on torch's current HIP stream, nothing falls back to the CPU.
                            separation_scan; no reference counterpart)
     intersample_pair_rows  the same scan as QP rows: per (agent, segment) the neighbours that pass too close between
     append_collision_rows  two nodes, appended to collision_rows' node rows (CouplingSpec.intersample_S)
+    fleet_obstacle_clearance  continuous-time closest approach of every agent to every obstacle (rollout_dense +
+    obstacle_scan          obstacle_scan); the scan's records are the obstacle rows of ObstacleRowsSpec
     pair_min_distance      node-level pairwise / agent-obstacle minimum distances
     obstacle_min_distance  (SCvx/utils/analysis.py:10-62)
 """
@@ -42,7 +44,8 @@ QUAD_PARAMS = (1.0, 9.81, 0.02, 0.02, 0.04)
 
 __all__ = ["model_dims", "model_id", "default_nsub", "foh_batched", "jacobi_update", "jacobi_update_global", "integrate_nonlinear", "collision_rows", "collision_check", "qp_solve_batched", "QPSpec", "SCPSpec", "SCPSolver", "slab_update",
            "intersample_batched", "rollout_dense", "separation_scan", "fleet_separation", "pair_min_distance",
-           "obstacle_min_distance", "intersample_pair_rows", "append_collision_rows",
+           "obstacle_min_distance", "intersample_pair_rows", "append_collision_rows", "obstacle_scan",
+           "fleet_obstacle_clearance",
            "disc_stride", "unpack_disc", "ScvxError", "MODEL_DIMS", "DEFAULT_NSUB"]
 
 
@@ -864,6 +867,101 @@ def append_collision_rows(X_all, i0, rec, count_seg, rows, count, pos_dim=3, idx
                                                   _dev(overflow, torch.int32, "overflow"), _stream(stream))
     check(rc, "scvx_collision_rows_append_batched")
     return rows, count, overflow
+
+
+def _obstacle_arrays(who, obstacles, device):
+    """[(centre, total radius)] -> device tensors centers (O,3), rho (O,); centres shorter than 3 are zero-padded
+    (P holds zeros past pos_dim).  A pair of tensors (centers, rho) made here before passes through."""
+    import numpy as np
+    torch = _torch()
+    if isinstance(obstacles, tuple) and len(obstacles) == 2 and all(isinstance(t, torch.Tensor) for t in obstacles):
+        if obstacles[0].dim() != 2 or obstacles[0].shape[1] != 3 or tuple(obstacles[1].shape) != (obstacles[0].shape[0],) \
+                or not obstacles[0].shape[0]:
+            raise ValueError(f"{who}: centers (O,3) and rho (O,) with O >= 1 expected")
+        return obstacles
+    obstacles = list(obstacles)
+    if not obstacles:
+        raise ValueError(f"{who}: at least one obstacle required")
+    c = np.zeros((len(obstacles), 3))
+    for o, (ctr, _) in enumerate(obstacles):
+        ctr = np.asarray(ctr, float).reshape(-1)
+        if not 1 <= ctr.size <= 3:
+            raise ValueError(f"{who}: obstacle centres must have 1..3 coordinates")
+        c[o, :ctr.size] = ctr
+    r = np.array([float(r) for _, r in obstacles])
+    return torch.as_tensor(c, device=device), torch.as_tensor(r, device=device)
+
+
+def obstacle_scan(P, obstacles, cull=None, J=0, analysis=True, stream=None):
+    """Continuous-time closest approach of every agent to every obstacle on the dense samples P (N,K-1,S+1,3) of
+    rollout_dense (scvx_obstacle_scan_batched).  obstacles: [(centre, total radius rho)], at least one, any number;
+    centres shorter than 3 are zero-padded to match P's zero columns past pos_dim.  Device tensors: dist (N,K-1,O)
+    every obstacle's minimum chord distance to its centre on every segment and alpha (N,K-1,O) its position in the
+    segment, alpha' = (s + a) / S (analysis=False leaves both out).  Exact for the piecewise-linear interpolant of
+    the samples: within max ||r''|| h^2 / 8 of the continuous minimum, h = 1 / ((K-1) S) in normalised time,
+    r = p - c.
+    J in 1..8 adds the records of the obstacle rows (K <= 64): per (agent, segment) the J obstacles of largest
+    v = rho - dist among those with v > -cull (cull None: the largest rho), 0 < alpha' < 1 and dist > 0, in
+    descending (v, then ascending o) order: rec (N,K-1,J,4) = (g, v) with g = c / dist the unit direction from the
+    centre at the closest approach, obs (N,K-1,J) int32 the obstacle (-1 past count), rec_alpha (N,K-1,J) = alpha'
+    and count (N,K-1) int32 -- the layout of intersample_pair_rows, so append_collision_rows takes them as they are."""
+    torch = _torch()
+    if P.dim() != 4 or P.shape[3] != 3 or P.shape[2] < 2 or P.shape[1] < 1:
+        raise ValueError("obstacle_scan: P (N,K-1,S+1,3) with K >= 2 and S >= 1 expected")
+    N, Km1, S = P.shape[0], P.shape[1], P.shape[2] - 1
+    J = int(J)
+    if S > 16 or not 0 <= J <= 8 or (J and Km1 >= 64) or not (J or analysis):
+        raise ValueError(f"obstacle_scan: S <= 16 and 0 <= J <= 8 required (records: K <= 64; J = 0 needs "
+                         f"analysis=True); got S={S}, J={J}, K={Km1 + 1}")
+    dev = P.device
+    cd, rd = _obstacle_arrays("obstacle_scan", obstacles, dev)
+    O = cd.shape[0]
+    cull = float(rd.max().item()) if cull is None else float(cull)
+    if J and not cull > 0.0:
+        raise ValueError(f"obstacle_scan: cull > 0 required, got {cull}")
+    out = {}
+    if analysis:
+        out["dist"] = torch.empty((N, Km1, O), dtype=torch.float64, device=dev)
+        out["alpha"] = torch.empty((N, Km1, O), dtype=torch.float64, device=dev)
+    if J:
+        out["rec"] = torch.empty((N, Km1, J, 4), dtype=torch.float64, device=dev)
+        out["obs"] = torch.empty((N, Km1, J), dtype=torch.int32, device=dev)
+        out["rec_alpha"] = torch.empty((N, Km1, J), dtype=torch.float64, device=dev)
+        out["count"] = torch.empty((N, Km1), dtype=torch.int32, device=dev)
+    ptr = lambda k, dt=None: _dev(out[k], dt, k) if k in out else None  # noqa: E731
+    rc = lib().scvx_obstacle_scan_batched(Km1 + 1, S, N, _dev(P, name="P"), O, _dev(cd, name="centers"),
+                                          _dev(rd, name="rho"), cull, J, ptr("dist"), ptr("alpha"), ptr("rec"),
+                                          ptr("obs", torch.int32), ptr("rec_alpha"), ptr("count", torch.int32),
+                                          _stream(stream))
+    check(rc, "scvx_obstacle_scan_batched")
+    return out
+
+
+def fleet_obstacle_clearance(model, X, U, sigma, obstacles, robot_radius=0.0, S=8, nsub=None, pos_dim=None,
+                             params=None, stream=None):
+    """rollout_dense + obstacle_scan of a whole fleet, the counterpart of fleet_separation: how close any agent
+    comes to any obstacle, between the nodes as well as at them.  obstacles: [(centre, radius r_o)].  Returns clear
+    (N,K-1,O) = dist - (r_o + robot_radius) per segment, tau (N,K-1,O) where in the segment it occurs, D (N,O) the
+    minimum over the segments (the continuous-time form of obstacle_min_distance's matrix), agent_min (N,), min
+    (float) and argmin = (i, o, k, tau) where it occurs, plus P, L (the samples).  The accuracy statement of
+    separation_scan applies with r = p - c the position relative to the (fixed) centre; for the double integrator
+    ||r''|| <= max(sigma^2 ||u||) in normalised time."""
+    torch = _torch()
+    obstacles = list(obstacles)
+    P, L = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim, params=params, stream=stream)
+    sc = obstacle_scan(P, obstacles, stream=stream)
+    total = torch.as_tensor([float(r) + float(robot_radius) for _, r in obstacles], dtype=torch.float64,
+                            device=X.device)
+    clear = sc["dist"] - total
+    out = dict(clear=clear, tau=sc["alpha"], P=P, L=L, D=clear.min(dim=1).values)
+    out["agent_min"] = out["D"].min(dim=1).values
+    O = clear.shape[2]
+    flat = int(clear.argmin().item())
+    i, rest = divmod(flat, clear.shape[1] * O)
+    k, o = divmod(rest, O)
+    out["min"] = float(clear[i, k, o].item())
+    out["argmin"] = (i, o, k, float(sc["alpha"][i, k, o].item()))
+    return out
 
 
 def pair_min_distance(X, rows=None, stream=None):

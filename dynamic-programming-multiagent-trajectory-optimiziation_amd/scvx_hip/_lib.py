@@ -29,7 +29,7 @@ EXPORTS = ("scvx_version", "scvx_last_error", "scvx_foh_batched", "scvx_integrat
            "scvx_rtc_integrate_nonlinear_batched", "scvx_rtc_subproblem_compile", "scvx_rtc_intersample_batched",
            "scvx_jacobi_update_costs_batched", "scvx_jacobi_global_rule", "scvx_rollout_dense_batched",
            "scvx_separation_scan_batched", "scvx_pair_min_distance_batched", "scvx_obstacle_min_distance_batched",
-           "scvx_intersample_pair_rows_batched", "scvx_collision_rows_append_batched")
+           "scvx_intersample_pair_rows_batched", "scvx_collision_rows_append_batched", "scvx_obstacle_scan_batched")
 SCVX_MAX_MODEL_PARAMS, SCVX_RTC_MAX_NX, SCVX_RTC_MAX_NU = 16, 16, 8
 
 
@@ -136,7 +136,11 @@ def lib():
                                                          i32, vp]
         L.scvx_collision_rows_append_batched.argtypes = [i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp,
                                                          vp, vp]
-        cpp = ctypes.POINTER(ctypes.c_char_p)
+        if not hasattr(L, "scvx_obstacle_scan_batched"):
+            raise ImportError(f"{LIB_PATH} lacks the obstacle scan entry point: rebuild it "
+                              f"(`make -C {os.path.dirname(HERE)}`)")
+        L.scvx_obstacle_scan_batched.argtypes = [i32, i32, i32, vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp]
+        cpp =ctypes.POINTER(ctypes.c_char_p)
         L.scvx_rtc_model_create.argtypes = [i32, i32, cpp, cpp, cpp, ctypes.c_char_p, ctypes.POINTER(vp)]
         L.scvx_rtc_model_source.argtypes = [vp]
         L.scvx_rtc_model_source.restype = ctypes.c_char_p

@@ -13,11 +13,11 @@ collision coupling is on, plus one scalar all_reduce for the global trust-region
 """
 import dataclasses
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Sequence
 
 from . import (QPSolver, QPSpec, append_collision_rows, collision_check, collision_rows, collision_rows_indexed,
-               default_nsub, fleet_separation, foh_batched, intersample_pair_rows, jacobi_update, jacobi_update_global,
-               model_dims, rollout_dense)
+               default_nsub, fleet_obstacle_clearance, fleet_separation, foh_batched, intersample_pair_rows,
+               jacobi_update, jacobi_update_global, model_dims, obstacle_scan, rollout_dense)
 
 
 def balanced_order(iters, world):
@@ -62,7 +62,21 @@ class HipBackend:
     def intersample_pair_rows(self, model, X, U, sigma, S, nsub, pos_dim, R, cull, J):
         """(rec, count_seg) of every agent of the iterate (X, U): the dense roll-out, then the pair-rows scan."""
         P, L = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim)
+        self.samples = (S, P)   # for obstacle_rows of the same step (the driver hands it on and clears it)
         out = intersample_pair_rows(P, L, 0, X.shape[0], R, cull, J)
+        return out["rec"], out["count"]
+
+    def obstacle_rows(self, model, X, U, sigma, S, nsub, pos_dim, obstacles, cull, J, P=None):
+        """(rec, count_seg) of the obstacle rows of every agent of the iterate (X, U): the dense roll-out (P: the
+        samples of this very iterate at the same S, when the step already has them), then the obstacle scan.  The
+        obstacles' device arrays are made once per list object."""
+        if P is None:
+            P, _ = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim)
+        cached = getattr(self, "_obs_dev", None)
+        if cached is None or cached[0] is not obstacles or cached[1][0].device != X.device:
+            from . import _obstacle_arrays
+            cached = self._obs_dev = (obstacles, _obstacle_arrays("obstacle_rows", obstacles, X.device))
+        out = obstacle_scan(P, cached[1], cull=cull, J=J, analysis=False)
         return out["rec"], out["count"]
 
     def append_collision_rows(self, X_all, i0, idx, rec, count_seg, rows, count, pos_dim, overflow):
@@ -104,6 +118,24 @@ class CouplingSpec:
     intersample_cull: float = 0.0   # pairs farther apart than this give no row; <= 0: 3R
 
 
+@dataclass
+class ObstacleRowsSpec:
+    """Continuous-time obstacle rows, JacobiSCvx(..., obstacle_rows=ObstacleRowsSpec()).  The QP's own
+    obstacle rows (QPSpec.obs) hold at the nodes only; with this option every step rolls the iterate out with S
+    samples per segment, the J obstacles per (agent, segment) whose surface the chords come closest to strictly
+    between two nodes (within cull of it) each become two node rows g.(p_t - pbar_t) >= v - S_t, and these are
+    appended behind whatever collision rows the node already has (node rows, then pair records, then obstacle
+    records).  They share the node's collision slack and w_coll; the QP kernel is not touched (no slack group of
+    its own at w_obs, no chord row inside the QP).  QPSpec.j_max is the total capacity per node: the node-level
+    collision rows get j_max - 2 intersample_J - 2 J of it.  Works with or without a CouplingSpec, at any world
+    size (per agent and local: no collective).  Built-in models only.  Build-side option; the reference's Jacobi
+    driver constrains the nodes only."""
+    S: int = 8                  # dense samples per segment
+    J: int = 2                  # obstacles kept per (agent, segment)
+    cull: float = 0.0           # obstacles whose surface stays farther than this give no row; <= 0: the largest rho
+    obstacles: Optional[Sequence] = None   # [(centre, total radius rho)]; None: QPSpec.obs, the node rows' list
+
+
 class JacobiSCvx:
     """Device-resident Jacobi SCvx for this rank's agents [i0, i0 + N_local) of N_total.
 
@@ -133,13 +165,16 @@ class JacobiSCvx:
              SCvx-it/s); with every agent resident at once (C3, C5) the agent order is kept (dealing the long
              solves first there only moves them onto shared CUs: C3 780 -> 764); "none" -- always agent order.
              Results do not depend on it.
+    obstacle_rows: an ObstacleRowsSpec adds continuous-time obstacle rows to every subproblem (see there); None
+             (default): off, nothing changes.  The rows share the node's collision slack and w_coll; the QP kernel is
+             not touched.
     """
 
     def __init__(self, spec: QPSpec, x_init, x_final, sigma, tr0: float, coupling: Optional[CouplingSpec] = None,
                  tr_rule: str = "per_agent", group=None, nsub: Optional[int] = None, backend=None,
                  on_fail: str = "halve", tr_max: Optional[float] = None, fused_update: bool = True,
                  tie_rtol: float = 1e-9, warm_start: bool = True, warm_max_status: int = 0,
-                 dispatch_order: str = "lpt"):
+                 dispatch_order: str = "lpt", obstacle_rows: Optional["ObstacleRowsSpec"] = None):
         import torch
         self.torch = torch
         self.backend = backend or HipBackend()
@@ -208,6 +243,41 @@ class JacobiSCvx:
                             rows_node=torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
                                                   device=self.device),
                             overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
+        self._ob = None   # continuous-time obstacle rows (obstacle_rows): settings and buffers
+        if obstacle_rows is not None:
+            if not isinstance(spec.model, str):
+                raise NotImplementedError("obstacle_rows: the dense roll-out is compiled for the built-in models only "
+                                          "(no runtime-compiled form)")
+            S, J = int(obstacle_rows.S), int(obstacle_rows.J)
+            if not 1 <= S <= 16 or not 1 <= J <= 8:
+                raise ValueError(f"ObstacleRowsSpec: 1 <= S <= 16 and 1 <= J <= 8 required, got {S}, {J}")
+            obstacles = list(spec.obs if obstacle_rows.obstacles is None else obstacle_rows.obstacles)
+            if not obstacles:
+                raise ValueError("ObstacleRowsSpec: no obstacles (neither in the option nor in QPSpec.obs)")
+            J_pair = self._is["J"] if self._is is not None else 0
+            j_node = spec.j_max - 2 * J_pair - 2 * J
+            if j_node < (1 if coupling is not None else 0):
+                raise ValueError(f"obstacle_rows: QPSpec.j_max = {spec.j_max} is the total capacity per node and must "
+                                 f"hold the 2 x J = {2 * J} obstacle rows"
+                                 + (f", the 2 x intersample_J = {2 * J_pair} pair rows" if J_pair else "")
+                                 + (" and at least one node-level row" if coupling is not None else ""))
+            cull = float(obstacle_rows.cull) if obstacle_rows.cull > 0 else max(float(r) for _, r in obstacles)
+            self._ob = dict(S=S, J=J, cull=cull, obstacles=obstacles, j_node=j_node, rec=None, count_seg=None,
+                            overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
+            if coupling is None:   # independent agents: the driver owns the rows, all of them obstacle rows
+                self.rows = torch.zeros((self.N, spec.K, spec.j_max, spec.pos_dim + 1), dtype=torch.float64,
+                                        device=self.device)
+                self.count = torch.zeros((self.N, spec.K), dtype=torch.int32, device=self.device)
+            elif self._is is not None:
+                self._is["j_node"] = j_node
+                self._is["rows_node"] = self._is["rows_node"][:, :, :j_node].contiguous()
+            else:
+                self._ob["rows_node"] = torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
+                                                    device=self.device)
+
+    def _records(self):
+        """The record sets appended behind the node rows, in order: pair records, then obstacle records."""
+        return [s for s in (self._is, self._ob) if s is not None]
 
     def _hi_buffers(self):
         """Rows, counts and a QPSolver at j_max_hi sized for all N local agents, allocated once: a re-solve
@@ -219,9 +289,10 @@ class JacobiSCvx:
                                              device=self.device),
                             count=torch.zeros((self.N, spec.K), dtype=torch.int32, device=self.device),
                             solver=self.backend.qp_solver(spec_hi, self.N, self.device))
-            if self._is is not None:   # the node-level share of j_max_hi, before the continuous-time rows join it
-                self._hi["rows_node"] = torch.zeros((self.N, spec.K, c.j_max_hi - 2 * self._is["J"], spec.pos_dim + 1),
-                                                    dtype=torch.float64, device=self.device)
+            if self._records():   # the node-level share of j_max_hi, before the continuous-time rows join it
+                j_node = c.j_max_hi - 2 * sum(s["J"] for s in self._records())
+                self._hi["rows_node"] = torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
+                                                    device=self.device)
         return self._hi
 
     def _enforce_all_rows(self, X_all, X, U, out):
@@ -244,17 +315,17 @@ class JacobiSCvx:
         idx = bad.nonzero().flatten()
         hi = self._hi_buffers()
         gidx = (idx + self.i0).to(torch.int32)
-        if self._is is None:
+        if not self._records():
             self.backend.collision_rows_indexed(X_all, gidx, c.R, c.j_max_hi, spec.pos_dim, c.cull_radius, hi["rows"],
                                                 hi["count"])
-        else:   # j_max_hi - 2J node rows, then the step's own continuous-time records of those agents
-            s = self._is
-            j_node = c.j_max_hi - 2 * s["J"]
+        else:   # j_max_hi - 2 (J_pair + J_obs) node rows, then the step's own continuous-time records of those agents
+            j_node = c.j_max_hi - 2 * sum(s["J"] for s in self._records())
             self.backend.collision_rows_indexed(X_all, gidx, c.R, j_node, spec.pos_dim, c.cull_radius,
                                                 hi["rows_node"], hi["count"])
             hi["rows"][:n_bad, :, :j_node].copy_(hi["rows_node"][:n_bad])
-            self.backend.append_collision_rows(X_all, self.i0, gidx, s["rec"], s["count_seg"], hi["rows"], hi["count"],
-                                               spec.pos_dim, s["overflow"])
+            for s in self._records():
+                self.backend.append_collision_rows(X_all, self.i0, gidx, s["rec"], s["count_seg"], hi["rows"],
+                                                   hi["count"], spec.pos_dim, s["overflow"])
         g = lambda t: t.index_select(0, idx).contiguous()  # noqa: E731
         o2 = hi["solver"].solve(g(self.disc), g(self.sigma), g(X), g(U), g(self.x_init), g(self.x_final), g(self.tr),
                                 hi["rows"][:n_bad], hi["count"][:n_bad], n=n_bad)
@@ -285,6 +356,15 @@ class JacobiSCvx:
                                       "(and L) across ranks before the scan, which is not implemented")
         return fleet_separation(self.spec.model, X, U, self.sigma, S=S, nsub=self.nsub, pos_dim=self.spec.pos_dim)
 
+    def obstacle_clearance(self, X, U, S=8):
+        """Continuous-time clearance of every agent to every obstacle at the iterate (X, U)
+        (scvx_hip.fleet_obstacle_clearance: S samples per segment, the FOH's substep count, the template's pos_dim)
+        -- the between-nodes check the node-level obstacle rows cannot give.  The obstacles are the obstacle_rows
+        option's, else QPSpec.obs; their radii are total radii (robot_radius = 0).  Per agent and local: any world."""
+        obstacles = self._ob["obstacles"] if self._ob is not None else list(self.spec.obs)
+        return fleet_obstacle_clearance(self.spec.model, X, U, self.sigma, obstacles, 0.0, S=S, nsub=self.nsub,
+                                        pos_dim=self.spec.pos_dim)
+
     def _mark(self, marks, name):
         """Record a timing event named `name` on the current (launch) stream (marks: list or None)."""
         if marks is not None:
@@ -296,7 +376,8 @@ class JacobiSCvx:
         """One SCvx iteration; returns the new (X, U) and the raw solver outputs.
         marks: optional list; (stage, event) pairs are appended on the launch stream -- "start", then
         the end of "foh", "gather" (all-gather), "rows" (collision rows), "isrows" (with CouplingSpec.intersample_S > 0: dense
-        roll-out, pair-rows scan and append), "qp" (the QP kernel),
+        roll-out, pair-rows scan and append), "obsrows" (with obstacle_rows: dense roll-out unless shared, obstacle scan and
+        append), "qp" (the QP kernel),
         "check" (full-row check + re-solve) and "update" (bookkeeping); a stage's time is the
         difference to the previous mark."""
         torch = self.torch
@@ -312,24 +393,45 @@ class JacobiSCvx:
                 work.wait()
             X_all = self.X_all
             self._mark(marks, "gather")
-            if self._is is None:
+            if not self._records():
                 rows, count = self.backend.collision_rows(X_all, self.i0, self.N, self.coupling.R, spec.j_max,
                                                           spec.pos_dim, self.coupling.cull_radius, self.rows, self.count)
                 self._mark(marks, "rows")
             else:
-                # the node rows take j_max - 2J slots of every node; the continuous-time rows of the current
-                # iterate (two per record: the segment's two nodes) follow them
-                s = self._is
-                self.backend.collision_rows(X_all, self.i0, self.N, self.coupling.R, s["j_node"], spec.pos_dim,
-                                            self.coupling.cull_radius, s["rows_node"], self.count)
-                self.rows[:, :, :s["j_node"]].copy_(s["rows_node"])
+                # the node rows take j_max - 2 (J_pair + J_obs) slots of every node; the continuous-time rows of the
+                # current iterate (two per record: the segment's two nodes) follow them
+                first = self._records()[0]
+                j_node, rows_node = first["j_node"], first["rows_node"]
+                self.backend.collision_rows(X_all, self.i0, self.N, self.coupling.R, j_node, spec.pos_dim,
+                                            self.coupling.cull_radius, rows_node, self.count)
+                self.rows[:, :, :j_node].copy_(rows_node)
+                rows, count = self.rows, self.count
                 self._mark(marks, "rows")
+            if self._is is not None:
+                s = self._is
                 s["rec"], s["count_seg"] = self.backend.intersample_pair_rows(
                     spec.model, X, U, self.sigma, s["S"], self.nsub, spec.pos_dim, self.coupling.R, s["cull"], s["J"])
                 s["overflow"].zero_()
                 rows, count, _ = self.backend.append_collision_rows(X_all, self.i0, None, s["rec"], s["count_seg"],
                                                                     self.rows, self.count, spec.pos_dim, s["overflow"])
                 self._mark(marks, "isrows")
+        if self._ob is not None:
+            s = self._ob
+            # the pair rows' samples of this iterate serve again when the sample counts agree
+            shared = getattr(self.backend, "samples", None) if self._is is not None else None
+            share = {"P": shared[1]} if shared is not None and shared[0] == s["S"] else {}
+            if shared is not None:
+                self.backend.samples = None
+            s["rec"], s["count_seg"] = self.backend.obstacle_rows(
+                spec.model, X, U, self.sigma, s["S"], self.nsub, spec.pos_dim, s["obstacles"], s["cull"], s["J"], **share)
+            s["overflow"].zero_()
+            if self.coupling is None:   # independent agents: no node rows, the iterate is its own X_all
+                self.count.zero_()
+                X_all = X if X.is_contiguous() else X.contiguous()
+            rows, count, _ = self.backend.append_collision_rows(X_all, self.i0 if self.coupling is not None else 0,
+                                                                None, s["rec"], s["count_seg"], self.rows, self.count,
+                                                                spec.pos_dim, s["overflow"])
+            self._mark(marks, "obsrows")
         kw = {"order": self.order} if self.order is not None else {}
         out = self.solver.solve(self.disc, self.sigma, X, U, self.x_init, self.x_final, self.tr, rows, count,
                                 warm=self.warm, **kw)
@@ -346,6 +448,8 @@ class JacobiSCvx:
                 # continuous-time rows that did not fit a node's capacity, in this step's solve and re-solve (none
                 # by construction: the node rows leave 2J slots free)
                 self.last_check["is_overflow"] = int(self._is["overflow"].item())
+            if self._ob is not None:   # the same for the obstacle rows
+                self.last_check["obs_overflow"] = int(self._ob["overflow"].item())
             self._mark(marks, "check")
         # an agent whose subproblem failed numerically (status 2) rejects the step: it keeps its
         # iterate (its output may be non-finite and would otherwise reach every other agent through

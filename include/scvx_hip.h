@@ -30,7 +30,8 @@ extern "C" {
 #define SCVX_HIP_VERSION 7   /* 7: fleet separation analysis (scvx_rollout_dense_batched, scvx_separation_scan_batched,
                                   scvx_pair_min_distance_batched, scvx_obstacle_min_distance_batched); the
                                   inter-sample collision rows (scvx_intersample_pair_rows_batched,
-                                  scvx_collision_rows_append_batched) were added to it without a bump: purely
+                                  scvx_collision_rows_append_batched) and the obstacle scan
+                                  (scvx_obstacle_scan_batched) were added to it without a bump: purely
                                   additive, no existing argument list changed */
 
 #define SCVX_OK 0
@@ -562,6 +563,34 @@ int scvx_collision_rows_append_batched(int K, int pos_dim, int n_x, int N_total,
                                        const int32_t* idx, int N_local, int J, const double* rec,
                                        const int32_t* count_seg, int j_max, double* rows, int32_t* count,
                                        int32_t* overflow, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Continuous-time agent-obstacle clearance and obstacle rows for the Jacobi QP (csrc/obstacle_rows.hip,
+ * DESIGN §3.8).  One entry point added to revision 7; no existing argument list changed.
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * Per agent and segment k < K-1 of the samples P [N][K-1][S+1][3] of scvx_rollout_dense_batched, against the
+ * obstacles centers [O][3] / rho [O] (device; rho the total radius, obstacle plus robot; O >= 1, no upper limit):
+ * obstacle o's closest approach on the segment is the chord formula of scvx_separation_scan_batched with
+ * d_s = p_s - c_o over the S sub-intervals (first minimum over s, replaced only when strictly smaller): (s, a),
+ * c = d0 + a e, dist = ||c||, alpha' = (s + a) / S, v = rho_o - dist.
+ * Analysis outputs (both or neither):
+ *     dist  [N][K-1][O]   alpha [N][K-1][O] = alpha'
+ * Record outputs (all four with 1 <= J <= 8, none with J = 0).  Obstacle o is a candidate when
+ *     v > -cull,   0 < alpha' < 1 (a minimum at a node belongs to the node rows),   dist > 0;
+ * the J candidates of largest v are kept, ties to the lower o, and written in descending (v, then ascending o)
+ * order in the layout of scvx_intersample_pair_rows_batched, so that scvx_collision_rows_append_batched turns
+ * them into node rows g'(p_t - pbar_t) >= v - S_t unchanged:
+ *     rec   [N][K-1][J][4]   g = c / dist (3 doubles, zeros past pos_dim when P and the centres hold zeros there), v
+ *     obs   [N][K-1][J]      int32 o            rec_alpha [N][K-1][J]   alpha'
+ *     count [N][K-1]         int32 records kept; slots past it hold zeros, obs -1
+ * Every (agent, segment) is computed on its own: a slice of P returns the matching rows of the full launch bit
+ * for bit.  Limits: K >= 2, 1 <= S <= 16, 0 <= J <= 8; with records K <= 64 (the append's) and cull > 0.
+ */
+int scvx_obstacle_scan_batched(int K, int S, int N, const double* P, int O, const double* centers, const double* rho,
+                               double cull, int J, double* dist, double* alpha, double* rec, int32_t* obs,
+                               double* rec_alpha, int32_t* count, void* stream);
 
 #ifdef __cplusplus
 }
