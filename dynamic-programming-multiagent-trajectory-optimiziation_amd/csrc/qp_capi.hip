@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <mutex>
 
 #include "common.hpp"
 #include "qp_caps.hpp"
@@ -27,6 +28,118 @@ bool qp_force_generic_k() {
 bool qp_force_generic_flags() {
     const char* e = std::getenv("SCVX_QP_GENERIC_FLAGS");
     return e && e[0] && !(e[0] == '0' && !e[1]);
+}
+
+// Split launch (scvx_qp_solve_batched_split).  Per device: one non-blocking side stream and the fork / join events
+// (timing disabled), created at the first split launch and kept for the life of the process.
+namespace {
+struct SplitDev {
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    int lds_cu = 0, lds_wg = 0;   // LDS bytes per compute unit / per workgroup
+    int cus = 0;                  // compute units
+    bool ok = false, tried = false;
+};
+constexpr int kMaxDev = 64;
+SplitDev g_split[kMaxDev];
+std::mutex g_split_mu;
+// kernels whose dynamic-LDS limit has been raised to `bytes` (the attribute is set once per kernel and size)
+struct SplitAttr { const void* fn; int bytes; };
+SplitAttr g_split_attr[32];
+int g_split_nattr = 0;
+// workgroups of kernel `fn` (one wave, `lds` bytes) a compute unit holds at once, asked once per kernel and size
+struct SplitOcc { const void* fn; size_t lds; int blocks; };
+SplitOcc g_split_occ[32];
+int g_split_nocc = 0;
+
+int split_blocks_per_cu(const void* fn, size_t lds) {
+    for (int i = 0; i < g_split_nocc; ++i)
+        if (g_split_occ[i].fn == fn && g_split_occ[i].lds == lds) return g_split_occ[i].blocks;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, WAVE, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        nb = 0;
+    }
+    if (g_split_nocc < 32) g_split_occ[g_split_nocc++] = {fn, lds, nb};
+    return nb;
+}
+
+SplitDev* split_dev() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return nullptr;
+    SplitDev& d = g_split[dev];
+    if (!d.tried) {
+        d.tried = true;
+        int cu = 0, wg = 0;
+        d.ok = hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+               hipDeviceGetAttribute(&cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess &&
+               hipDeviceGetAttribute(&wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
+               hipStreamCreateWithFlags(&d.side, hipStreamNonBlocking) == hipSuccess &&
+               hipEventCreateWithFlags(&d.fork, hipEventDisableTiming) == hipSuccess &&
+               hipEventCreateWithFlags(&d.join, hipEventDisableTiming) == hipSuccess;
+        d.lds_cu = cu; d.lds_wg = wg;
+        if (!d.ok) (void)hipGetLastError();
+    }
+    return d.ok ? &d : nullptr;
+}
+}  // namespace
+
+// The tail's LDS request: WHOLE -- what is left next to it does not hold one more QP workgroup (lds bytes each);
+// HALF -- it holds one and a half, so exactly one fits whatever the allocation granule.  0: no such request exists
+// (the kernel's own request already is that large, or exceeds the workgroup limit).
+static int split_tail_lds(int reserve, size_t lds, int lds_cu, int lds_wg) {
+    const long long room = reserve == SCVX_QP_RESERVE_HALF ? (long long)lds + (long long)lds / 2 : (long long)lds / 2;
+    long long req = (long long)lds_cu - room;
+    if (req > lds_wg) req = lds_wg;
+    if (req < (long long)lds || (long long)lds_cu - req >= (reserve == SCVX_QP_RESERVE_HALF ? 2 : 1) * (long long)lds)
+        return 0;
+    return (int)(req & ~15LL);
+}
+
+int qp_launch_split(const void* fn, const QPArgs& a, size_t lds, hipStream_t st) {
+    std::lock_guard<std::mutex> lock(g_split_mu);
+    QPArgs bulk = a;
+    bulk.tail_n = 0; bulk.order_tail = nullptr;
+    void* kargs[] = {(void*)&bulk};
+    SplitDev* d = split_dev();
+    const int tail_lds = d ? split_tail_lds(a.tail_reserve, lds, d->lds_cu, d->lds_wg) : 0;
+    // The split is for a launch whose workgroups are all resident at once (then it lasts as long as its slowest one):
+    // where the kernel's registers and LDS let fewer share the compute units, the agents run in rounds already and
+    // reserved compute units only lengthen the queue, so they are dealt in one launch.
+    bool split = d && tail_lds > 0 && (long long)a.N <= (long long)d->cus * split_blocks_per_cu(fn, lds);
+    if (split && tail_lds > 65536) {
+        bool have = false;
+        for (int i = 0; i < g_split_nattr; ++i) have = have || (g_split_attr[i].fn == fn && g_split_attr[i].bytes >= tail_lds);
+        if (!have) {
+            split = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, tail_lds) == hipSuccess;
+            if (split && g_split_nattr < 32) g_split_attr[g_split_nattr++] = {fn, tail_lds};
+        }
+    }
+    if (split) {
+        // fork: both launches come behind everything already on `st`.  The tail must reach the compute units first (a
+        // tail workgroup that finds them full waits until one has drained completely: the step then takes 1.36 ms
+        // instead of 1.10, DESIGN §3.3 "Split launch"), so it is the tail that stays on `st`, where it starts as soon
+        // as its predecessor ends, and the bulk that crosses to the side stream, which costs it the ~7 us of the
+        // event hand-over.
+        QPArgs tail = bulk;
+        tail.order = a.order_tail;
+        void* targs[] = {(void*)&tail};
+        split = hipEventRecord(d->fork, st) == hipSuccess && hipStreamWaitEvent(d->side, d->fork, 0) == hipSuccess &&
+                hipLaunchKernel(fn, dim3(a.tail_n), dim3(WAVE), targs, (size_t)tail_lds, st) == hipSuccess;
+    }
+    if (!split) {
+        // no side stream, no such LDS request or a refused tail launch: every agent in one launch, in agent order
+        (void)hipGetLastError();
+        bulk.order = nullptr;
+        (void)hipLaunchKernel(fn, dim3(a.N), dim3(WAVE), kargs, lds, st);
+        return check_launch("qp_ipm_kernel");
+    }
+    if (hipLaunchKernel(fn, dim3(a.N), dim3(WAVE), kargs, lds, d->side) != hipSuccess)
+        return check_launch("qp_ipm_kernel (bulk)");
+    // join: whatever follows on `st` comes behind both launches
+    if (hipEventRecord(d->join, d->side) != hipSuccess || hipStreamWaitEvent(st, d->join, 0) != hipSuccess)
+        return check_launch("qp_ipm_kernel (split join)");
+    return check_launch("qp_ipm_kernel");
 }
 }  // namespace scvx
 
@@ -139,13 +252,14 @@ extern "C" size_t scvx_qp_workspace_bytes(const scvx_qp_template* tpl, int N) {
     return ws_bytes(c, N, tpl->K);
 }
 
-extern "C" int scvx_qp_solve_batched_ordered(const scvx_qp_template* tpl, int N, const double* disc,
-                                             const double* sigma, const double* Xref, const double* Uref,
-                                             const double* x_init, const double* x_final, const double* tr,
-                                             const double* coll_rows, const int32_t* coll_count, double* X, double* U,
-                                             double* slack_coll, double* nu, double* obj, int32_t* status,
-                                             int32_t* iters, const int32_t* warm, const int32_t* order,
-                                             void* workspace, size_t workspace_bytes, void* stream) {
+// the solve behind the three entry points: order_tail / T / reserve are those of scvx_qp_solve_batched_split
+// (T = 0: one launch)
+static int qp_solve(const scvx_qp_template* tpl, int N, const double* disc, const double* sigma, const double* Xref,
+                    const double* Uref, const double* x_init, const double* x_final, const double* tr,
+                    const double* coll_rows, const int32_t* coll_count, double* X, double* U, double* slack_coll,
+                    double* nu, double* obj, int32_t* status, int32_t* iters, const int32_t* warm,
+                    const int32_t* order, const int32_t* order_tail, int T, int reserve, void* workspace,
+                    size_t workspace_bytes, void* stream) {
     QPClass c;
     int rc = qp_check(tpl, N, c);
     if (rc != SCVX_OK) return rc;
@@ -170,8 +284,38 @@ extern "C" int scvx_qp_solve_batched_ordered(const scvx_qp_template* tpl, int N,
     a.ws_agent = (long long)(need / sizeof(double) / (size_t)N);
     a.trace = g_trace; a.trace_agent = g_trace_agent; a.trace_cap = g_trace_cap;
     a.order = order;
-    if (c.rt) return rtc_qp_launch(a, c.nb, c.no, c.nc, c.vc, (hipStream_t)stream);
+    if (c.rt) {   // the runtime-compiled classes keep the single launch (the two lists of a split: agent order)
+        if (T > 0) a.order = nullptr;
+        return rtc_qp_launch(a, c.nb, c.no, c.nc, c.vc, (hipStream_t)stream);
+    }
+    a.order_tail = order_tail; a.tail_n = T; a.tail_reserve = reserve;
     return c.mt->launch(c.cls, a, (hipStream_t)stream);
+}
+
+extern "C" int scvx_qp_solve_batched_ordered(const scvx_qp_template* tpl, int N, const double* disc,
+                                             const double* sigma, const double* Xref, const double* Uref,
+                                             const double* x_init, const double* x_final, const double* tr,
+                                             const double* coll_rows, const int32_t* coll_count, double* X, double* U,
+                                             double* slack_coll, double* nu, double* obj, int32_t* status,
+                                             int32_t* iters, const int32_t* warm, const int32_t* order,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+    return qp_solve(tpl, N, disc, sigma, Xref, Uref, x_init, x_final, tr, coll_rows, coll_count, X, U, slack_coll, nu,
+                    obj, status, iters, warm, order, nullptr, 0, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int scvx_qp_solve_batched_split(const scvx_qp_template* tpl, int N, const double* disc, const double* sigma,
+                                           const double* Xref, const double* Uref, const double* x_init,
+                                           const double* x_final, const double* tr, const double* coll_rows,
+                                           const int32_t* coll_count, double* X, double* U, double* slack_coll,
+                                           double* nu, double* obj, int32_t* status, int32_t* iters,
+                                           const int32_t* warm, const int32_t* order_bulk, const int32_t* order_tail,
+                                           int T, int reserve, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N > 0 && (!order_bulk || !order_tail)) return set_error(SCVX_EINVAL, "qp split: null order list");
+    if (T < 1 || T > (N > 0 ? N : 1)) return set_error(SCVX_EINVAL, "qp split: 1 <= T <= N required");
+    if (reserve != SCVX_QP_RESERVE_WHOLE && reserve != SCVX_QP_RESERVE_HALF)
+        return set_error(SCVX_EINVAL, "qp split: reserve must be SCVX_QP_RESERVE_WHOLE or SCVX_QP_RESERVE_HALF");
+    return qp_solve(tpl, N, disc, sigma, Xref, Uref, x_init, x_final, tr, coll_rows, coll_count, X, U, slack_coll, nu,
+                    obj, status, iters, warm, order_bulk, order_tail, T, reserve, workspace, workspace_bytes, stream);
 }
 
 extern "C" int scvx_qp_solve_batched(const scvx_qp_template* tpl, int N, const double* disc, const double* sigma,

@@ -111,10 +111,12 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
     const int K = KC > 0 ? KC : T.K, lane = threadIdx.x, t = lane;
     // dispatch order: workgroups start in index order as slots free up, so when the agents outnumber the resident
     // waves (C4: 4096 agents, 1024 at a time) the host can deal the longest solves first (scvx_qp_solve_batched_ordered);
-    // an entry outside [0, N) falls back to the workgroup's own index
+    // an entry outside [0, N) falls back to the workgroup's own index, but for SCVX_QP_ORDER_SKIP: that workgroup has
+    // no agent (the unused entries of the split launch's two lists) and returns before it reads or writes anything else
     long long agent = blockIdx.x;
     if (a.order) {
         const int o = a.order[blockIdx.x];
+        if (o == SCVX_QP_ORDER_SKIP) return;
         agent = (o >= 0 && o < a.N) ? o : (long long)blockIdx.x;
     }
     const bool act = t < K;
@@ -3271,12 +3273,18 @@ __global__ __launch_bounds__(64) void qp_ipm_kernel(QPArgs a) {
 }
 
 #ifndef __HIPCC_RTC__
+// The split launch of kernel `fn` (an instantiation of qp_ipm_kernel whose own LDS request is `lds` bytes): the
+// agents of a.order_tail on the library's side stream with the LDS request of a.tail_reserve, then those of a.order on
+// `st` (qp_capi.hip; scvx_qp_solve_batched_split of include/scvx_hip.h)
+int qp_launch_split(const void* fn, const QPArgs& a, size_t lds, hipStream_t st);
+
 // launch helpers (qp_capi.hip picks the instantiation)
 template <class C, int KC = 0, class F = QPFlagsRT>
 int qp_launch(const QPArgs& a, hipStream_t st) {
     if (KC > 0 && a.T.K != KC) return set_error(SCVX_EINVAL, "qp: K-specialised instantiation launched at another K");
     const size_t lds = sizeof(double) * (size_t)C::L.lds_doubles(a.T.K);
     if (lds > 65536) (void)hipFuncSetAttribute((const void*)qp_ipm_kernel<C, KC, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (a.tail_n > 0) return qp_launch_split((const void*)qp_ipm_kernel<C, KC, F>, a, lds, st);
     hipLaunchKernelGGL((qp_ipm_kernel<C, KC, F>), dim3(a.N), dim3(WAVE), lds, st, a);
     return check_launch("qp_ipm_kernel");
 }

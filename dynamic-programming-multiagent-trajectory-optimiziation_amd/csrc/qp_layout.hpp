@@ -35,6 +35,10 @@ struct QPArgs {
     double* trace;       // optional per-iteration diagnostics of agent `trace_agent` (or nullptr)
     int trace_agent, trace_cap;
     const int32_t* order;  // optional dispatch order: workgroup b solves agent order[b] (nullptr: agent b)
+    // host side only (the split launch, qp_capi.hip qp_launch_split; the kernel reads none of them): tail_n > 0 runs
+    // the agents of order_tail[tail_n] in a launch of their own with the LDS request of tail_reserve, `order` the rest
+    const int32_t* order_tail;
+    int tail_n, tail_reserve;
 };
 
 // byte offset of every access of a lane without a node (t >= K): beyond num_records of any workspace

@@ -324,6 +324,8 @@ class QPSolver:
         # slots [0, _state_n) hold a solve's primal-dual state (solve(n=...) always fills a leading prefix):
         # a warm flag on any other slot would start the IPM from uninitialised workspace, so it is cleared
         self._state_n = 0
+        self._order_tail = self._order_bulk = None   # dispatch_lists' buffers
+        self.last_entry = None
 
     def _check_shapes(self, disc, sigma, Xref, Uref, x_init, x_final, tr, coll_rows, coll_count, N=None):
         """Host-side shape checks: the kernel indexes every buffer with the template's compile-time
@@ -349,15 +351,45 @@ class QPSolver:
                 raise ValueError(f"QPSolver.solve: {name} has shape {tuple(t.shape)}, expected {shp}")
 
     supports_order = True
+    supports_split = True
+
+    def dispatch_lists(self, thr, T, short_per_tail=0, stream=None):
+        """The dispatch lists of the next solve from the IPM iteration counts this solver's last full solve left in
+        its `iters` buffer (scvx_qp_dispatch_select: one launch, no host sync): (order_tail (T,), order_bulk (N,)),
+        int32 device tensors reused by every call.  The agents sorted longest-first (stable); the first
+        min(T, #{iters >= thr}) go to the tail list -- with short_per_tail > 0 at most #{iters < thr} /
+        short_per_tail of them: the bulk workgroups each tail workgroup displaces must be short solves -- the rest
+        to the bulk list, unused entries are _lib.SCVX_QP_ORDER_SKIP.  T = 0: (None, the whole sort) -- the order of
+        solve(order=...)."""
+        torch = _torch()
+        T = int(T)
+        if not 0 <= T <= self.N:
+            raise ValueError(f"QPSolver.dispatch_lists: T={T} outside [0, {self.N}]")
+        if self._state_n < self.N:
+            raise ValueError("QPSolver.dispatch_lists: no full solve yet (the iteration counts are not set)")
+        if self._order_bulk is None:
+            self._order_bulk = torch.empty(self.N, dtype=torch.int32, device=self.iters.device)
+        if T > 0 and (self._order_tail is None or self._order_tail.numel() != T):
+            self._order_tail = torch.empty(T, dtype=torch.int32, device=self.iters.device)
+        tail = self._order_tail if T > 0 else None
+        rc = lib().scvx_qp_dispatch_select(self.N, _dev(self.iters, torch.int32), int(thr), T, int(short_per_tail),
+                                           int(self.spec.max_iter),
+                                           _dev(tail, torch.int32) if T > 0 else None,
+                                           _dev(self._order_bulk, torch.int32), _stream(stream))
+        check(rc, "scvx_qp_dispatch_select")
+        return tail, self._order_bulk
 
     def solve(self, disc, sigma, Xref, Uref, x_init, x_final, tr, coll_rows=None, coll_count=None, stream=None, n=None,
-              warm=None, order=None):
+              warm=None, order=None, order_tail=None, reserve="whole"):
         """n (<= N): solve only n agents (the inputs' leading dimension); the outputs are the leading n rows
         of the solver's buffers.  warm (N,) int32 device tensor or None: agents with warm != 0 start from the
         primal-dual point of their previous solve by THIS solver (the same agent slot), e.g. the previous
         SCvx iteration's status == 0.  order (n,) int32 device tensor or None: the dispatch order, a
-        permutation of range(n) (scvx_qp_solve_batched_ordered; results do not depend on it).  Returns dict
-        of device tensors (views of reused buffers)."""
+        permutation of range(n) (scvx_qp_solve_batched_ordered; results do not depend on it).  order_tail (T,)
+        int32 device tensor: the split launch (scvx_qp_solve_batched_split) -- these agents in a launch of their
+        own whose workgroups keep a compute unit to themselves (reserve "whole") or share it with one other
+        ("half"), `order` then the bulk list (dispatch_lists gives both).  Returns dict of device tensors (views of
+        reused buffers)."""
         torch = _torch()
         n = self.N if n is None else int(n)
         if not 0 <= n <= self.N:
@@ -376,15 +408,28 @@ class QPSolver:
         if order is not None and (tuple(order.shape) != (n,) or order.dtype != torch.int32):
             raise ValueError(f"QPSolver.solve: order must be an int32 ({n},) permutation, got "
                              f"{tuple(order.shape)} {order.dtype}")
-        rc = lib().scvx_qp_solve_batched_ordered(
+        split = ()
+        if order_tail is not None:
+            if order is None:
+                raise ValueError("QPSolver.solve: order_tail needs order, the bulk list (dispatch_lists)")
+            if order_tail.dim() != 1 or not 1 <= order_tail.numel() <= n or order_tail.dtype != torch.int32:
+                raise ValueError(f"QPSolver.solve: order_tail must be an int32 (T,) list with 1 <= T <= {n}, got "
+                                 f"{tuple(order_tail.shape)} {order_tail.dtype}")
+            if reserve not in _lib.SCVX_QP_RESERVE:
+                raise ValueError(f"QPSolver.solve: reserve must be 'whole' or 'half', not {reserve!r}")
+            split = (_dev(order_tail, torch.int32, "order_tail"), int(order_tail.numel()),
+                     _lib.SCVX_QP_RESERVE[reserve])
+        entry = "scvx_qp_solve_batched_split" if split else "scvx_qp_solve_batched_ordered"
+        rc = getattr(lib(), entry)(
             ctypes.byref(self.ctpl), n, _dev(disc, name="disc"), _dev(sigma, name="sigma"),
             _dev(Xref, name="Xref"), _dev(Uref, name="Uref"), _dev(x_init, name="x_init"), _dev(xf, name="x_final"),
             _dev(tr, name="tr"), _dev(coll_rows, name="coll_rows"), _dev(coll_count, torch.int32, "coll_count"),
             _dev(self.X), _dev(self.U), _dev(self.slack), _dev(self.nu), _dev(self.obj), _dev(self.status, torch.int32),
             _dev(self.iters, torch.int32), _dev(warm, torch.int32, "warm") if warm is not None else None,
-            _dev(order, torch.int32, "order") if order is not None else None,
+            _dev(order, torch.int32, "order") if order is not None else None, *split,
             _dev(self.workspace), ctypes.c_size_t(self.workspace.numel() * 8), _stream(stream))
-        check(rc, "scvx_qp_solve_batched_ordered")
+        check(rc, entry)
+        self.last_entry = entry   # (diagnostics: the entry point the last solve went through)
         self._state_n = max(self._state_n, n)
         out = self._outputs()
         return out if n == self.N else {k: v[:n] for k, v in out.items()}

@@ -18,6 +18,9 @@ MODEL_IDS = {"di": 0, "unicycle": 1, "si": 2, "quad": 3}
 MODEL_DIMS = {"di": (6, 3), "unicycle": (3, 2), "si": (3, 3), "quad": (12, 4)}
 SCVX_MODEL_RUNTIME = 255   # any other model: the subproblem kernels are compiled for its (n_x, n_u) at run time
 STATUS = {0: "optimal", 1: "optimal_inaccurate", 2: "solver_error"}
+# the split QP launch (include/scvx_hip.h): the order entry of a workgroup without an agent, the tail's reservation
+SCVX_QP_ORDER_SKIP = -2 ** 31
+SCVX_QP_RESERVE = {"whole": 1, "half": 2}
 
 # every symbol declared in include/scvx_hip.h
 EXPORTS = ("scvx_version", "scvx_last_error", "scvx_foh_batched", "scvx_integrate_nonlinear_batched",
@@ -29,7 +32,8 @@ EXPORTS = ("scvx_version", "scvx_last_error", "scvx_foh_batched", "scvx_integrat
            "scvx_rtc_integrate_nonlinear_batched", "scvx_rtc_subproblem_compile", "scvx_rtc_intersample_batched",
            "scvx_jacobi_update_costs_batched", "scvx_jacobi_global_rule", "scvx_rollout_dense_batched",
            "scvx_separation_scan_batched", "scvx_pair_min_distance_batched", "scvx_obstacle_min_distance_batched",
-           "scvx_intersample_pair_rows_batched", "scvx_collision_rows_append_batched", "scvx_obstacle_scan_batched")
+           "scvx_intersample_pair_rows_batched", "scvx_collision_rows_append_batched", "scvx_obstacle_scan_batched",
+           "scvx_qp_dispatch_select", "scvx_qp_solve_batched_split")
 SCVX_MAX_MODEL_PARAMS, SCVX_RTC_MAX_NX, SCVX_RTC_MAX_NU = 16, 16, 8
 
 
@@ -140,6 +144,12 @@ def lib():
             raise ImportError(f"{LIB_PATH} lacks the obstacle scan entry point: rebuild it "
                               f"(`make -C {os.path.dirname(HERE)}`)")
         L.scvx_obstacle_scan_batched.argtypes = [i32, i32, i32, vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp]
+        if not hasattr(L, "scvx_qp_solve_batched_split"):
+            raise ImportError(f"{LIB_PATH} lacks the split QP launch entry points: rebuild it "
+                              f"(`make -C {os.path.dirname(HERE)}`)")
+        L.scvx_qp_dispatch_select.argtypes = [i32, vp, i32, i32, i32, i32, vp, vp, vp]
+        L.scvx_qp_solve_batched_split.argtypes = ([ctypes.POINTER(QPTemplate), i32] + [vp] * 19 + [i32, i32]
+                                                  + [vp, sz, vp])
         cpp =ctypes.POINTER(ctypes.c_char_p)
         L.scvx_rtc_model_create.argtypes = [i32, i32, cpp, cpp, cpp, ctypes.c_char_p, ctypes.POINTER(vp)]
         L.scvx_rtc_model_source.argtypes = [vp]

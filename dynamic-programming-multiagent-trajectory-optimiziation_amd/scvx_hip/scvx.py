@@ -12,12 +12,18 @@ collective is one all_gather of the states per iteration (RCCL over xGMI), neede
 collision coupling is on, plus one scalar all_reduce for the global trust-region rule.
 """
 import dataclasses
+import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
 from . import (QPSolver, QPSpec, append_collision_rows, collision_check, collision_rows, collision_rows_indexed,
                default_nsub, fleet_obstacle_clearance, fleet_separation, foh_batched, intersample_pair_rows,
                jacobi_update, jacobi_update_global, model_dims, obstacle_scan, rollout_dense)
+
+# The split QP launch of JacobiSCvx (dispatch_order="lpt", every agent resident): the measured settings of
+# profiles/split_sweep.txt (DESIGN §3.3 "Split launch").  SPLIT_DEFAULT: what an unset SCVX_QP_SPLIT stands for ("1": on
+# where the driver's rule applies, "0": the single launch).
+SPLIT_THR, SPLIT_T, SPLIT_RESERVE, SPLIT_DEFAULT = 7, 64, "whole", "1"
 
 
 def balanced_order(iters, world):
@@ -162,9 +168,21 @@ class JacobiSCvx:
     dispatch_order: "lpt" (default) -- when the agents outnumber the resident waves (one per SIMD: 4 x the
              GPU's CUs; C4), each QP launch deals them longest-first by their previous solve's IPM iterations
              (QPSolver.solve(order=...)), so a slot that frees up takes the next-longest solve (C4 85 -> 93
-             SCvx-it/s); with every agent resident at once (C3, C5) the agent order is kept (dealing the long
-             solves first there only moves them onto shared CUs: C3 780 -> 764); "none" -- always agent order.
-             Results do not depend on it.
+             SCvx-it/s); "none" -- always agent order, one launch.  Results do not depend on it.
+             With every agent resident at once (C3, C5) an order alone gains nothing (dealing the long solves first
+             only moves them onto shared CUs: C3 780 -> 764), but the launch lasts as long as its slowest wave, and
+             the slowest agents are the same from step to step: where the agents outnumber the CUs, "lpt" launches
+             the QP kernel twice (QPSolver.solve(order_tail=...), scvx_qp_solve_batched_split) -- the up to split_T
+             agents whose last solve took at least split_thr IPM iterations on compute units they share with nobody
+             (split_reserve "whole") or with one workgroup ("half"), everyone else as before, longest first.  A
+             step in which no agent reached split_thr launches no tail agent, nor does one without
+             split_short_per_tail shorter solves per tail agent (default: what a tail workgroup displaces, 3 or 1).
+             The lists come from one selection launch (QPSolver.dispatch_lists), which also orders the
+             agents-outnumber-waves case.  Built-in models and tr_rule="global" only (under the per-agent rule most
+             steps have no tail and the fixed cost of two launches is all that is left: c3 -1.4 %).  The environment
+             variable SCVX_QP_SPLIT=0 turns the split off (2: on also under the per-agent rule and where the agents
+             do not outnumber the CUs); SCVX_QP_SPLIT_THR / _T / _RESERVE override the three settings (DESIGN §3.3
+             "Split launch").
     obstacle_rows: an ObstacleRowsSpec adds continuous-time obstacle rows to every subproblem (see there); None
              (default): off, nothing changes.  The rows share the node's collision slack and w_coll; the QP kernel is
              not touched.
@@ -174,7 +192,9 @@ class JacobiSCvx:
                  tr_rule: str = "per_agent", group=None, nsub: Optional[int] = None, backend=None,
                  on_fail: str = "halve", tr_max: Optional[float] = None, fused_update: bool = True,
                  tie_rtol: float = 1e-9, warm_start: bool = True, warm_max_status: int = 0,
-                 dispatch_order: str = "lpt", obstacle_rows: Optional["ObstacleRowsSpec"] = None):
+                 dispatch_order: str = "lpt", obstacle_rows: Optional["ObstacleRowsSpec"] = None,
+                 split_thr: Optional[int] = None, split_T: Optional[int] = None,
+                 split_reserve: Optional[str] = None, split_short_per_tail: Optional[int] = None):
         import torch
         self.torch = torch
         self.backend = backend or HipBackend()
@@ -197,9 +217,28 @@ class JacobiSCvx:
             raise ValueError(f"dispatch_order must be 'lpt' or 'none', not {dispatch_order!r}")
         self.dispatch_order = dispatch_order
         self.order = None  # (N,) int32 device: the next launch's dispatch order (longest previous solve first)
-        resident = 4 * torch.cuda.get_device_properties(self.device).multi_processor_count \
-            if self.device.type == "cuda" else self.N
+        cus = self._cu_count()
+        resident = 4 * cus if cus else self.N
         self._lpt = dispatch_order == "lpt" and self.N > resident
+        env = os.environ.get
+        self.split_thr = int(env("SCVX_QP_SPLIT_THR") or (SPLIT_THR if split_thr is None else split_thr))
+        self.split_T = min(int(env("SCVX_QP_SPLIT_T") or (SPLIT_T if split_T is None else split_T)), self.N)
+        self.split_reserve = env("SCVX_QP_SPLIT_RESERVE") or (SPLIT_RESERVE if split_reserve is None else split_reserve)
+        if self.split_reserve not in ("whole", "half"):
+            raise ValueError(f"split_reserve must be 'whole' or 'half', not {self.split_reserve!r}")
+        # a tail workgroup displaces the other three of its CU (one, sharing half of it) into a second round: the
+        # selection forms a tail only while that many short solves per tail agent exist (0: no such limit)
+        self.split_short_per_tail = int((3 if self.split_reserve == "whole" else 1) if split_short_per_tail is None
+                                        else split_short_per_tail)
+        # agents that do not outnumber the CUs share none: nothing to reserve (C2).  Under the per-agent rule every
+        # agent's radius settles on its own and the counts level out at 5-6: most steps have no tail and would only pay
+        # the two launches' fixed cost (c3: -1.4 %), so the split is for the global rule.  SCVX_QP_SPLIT=2 asks for it
+        # in both cases.
+        mode = env("SCVX_QP_SPLIT", SPLIT_DEFAULT)
+        self._split = (dispatch_order == "lpt" and not self._lpt and bool(cus) and self.split_T >= 1
+                       and isinstance(spec.model, str) and mode != "0"
+                       and ((self.N > cus and tr_rule == "global") or mode == "2"))
+        self.order_tail = None  # (split_T,) int32 device: the next launch's tail list (split launch)
         self.group = group
         # RK4 substeps of the FOH: default_nsub for this run's longest interval (one host read of max(sigma) here,
         # none per step; the quadrotor's count grows with the interval)
@@ -274,6 +313,12 @@ class JacobiSCvx:
             else:
                 self._ob["rows_node"] = torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
                                                     device=self.device)
+
+    def _cu_count(self):
+        """Compute units of this driver's GPU (0: no GPU -- stub backends; every dispatch option is then off)"""
+        if self.device.type != "cuda":
+            return 0
+        return int(self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def _records(self):
         """The record sets appended behind the node rows, in order: pair records, then obstacle records."""
@@ -433,6 +478,8 @@ class JacobiSCvx:
                                                                 spec.pos_dim, s["overflow"])
             self._mark(marks, "obsrows")
         kw = {"order": self.order} if self.order is not None else {}
+        if self.order_tail is not None:
+            kw.update(order_tail=self.order_tail, reserve=self.split_reserve)
         out = self.solver.solve(self.disc, self.sigma, X, U, self.x_init, self.x_final, self.tr, rows, count,
                                 warm=self.warm, **kw)
         if self.warm_start:   # one launch: the comparison written straight into the int32 flag buffer
@@ -440,7 +487,13 @@ class JacobiSCvx:
                 self._warm_buf = torch.empty((self.N,), dtype=torch.int32, device=self.device)
             self.warm = torch.le(out["status"], self.warm_max_status, out=self._warm_buf)
         if self._lpt and getattr(self.solver, "supports_order", False):
-            self.order = torch.argsort(out["iters"], descending=True, stable=True).to(torch.int32)
+            if getattr(self.solver, "supports_split", False):   # one launch: the stable longest-first sort
+                self.order = self.solver.dispatch_lists(self.spec.max_iter + 1, 0)[1]
+            else:
+                self.order = torch.argsort(out["iters"], descending=True, stable=True).to(torch.int32)
+        elif self._split and getattr(self.solver, "supports_split", False):
+            self.order_tail, self.order = self.solver.dispatch_lists(self.split_thr, self.split_T,
+                                                                     self.split_short_per_tail)
         self._mark(marks, "qp")
         if self.coupling is not None and self.coupling.check:
             out = self._enforce_all_rows(X_all, X, U, out)

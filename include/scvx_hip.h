@@ -32,7 +32,8 @@ extern "C" {
                                   inter-sample collision rows (scvx_intersample_pair_rows_batched,
                                   scvx_collision_rows_append_batched) and the obstacle scan
                                   (scvx_obstacle_scan_batched) were added to it without a bump: purely
-                                  additive, no existing argument list changed */
+                                  additive, no existing argument list changed; likewise the split QP launch
+                                  (scvx_qp_dispatch_select, scvx_qp_solve_batched_split) */
 
 #define SCVX_OK 0
 #define SCVX_EINVAL (-1)
@@ -221,6 +222,44 @@ int scvx_qp_solve_batched_ordered(const scvx_qp_template* tpl, int N, const doub
                                   const int32_t* coll_count, double* X, double* U, double* slack_coll, double* nu,
                                   double* obj, int32_t* status, int32_t* iters, const int32_t* warm,
                                   const int32_t* order, void* workspace, size_t workspace_bytes, void* stream);
+
+/* An order entry with this value makes its workgroup return before it reads or writes anything (every other entry
+ * outside [0, N) falls back to the workgroup's index, as above). */
+#define SCVX_QP_ORDER_SKIP (-2147483647 - 1)
+/* tail reservation of scvx_qp_solve_batched_split: the tail workgroup's LDS request leaves room for no other QP
+ * workgroup on its compute unit (WHOLE) or for exactly one (HALF) */
+#define SCVX_QP_RESERVE_WHOLE 1
+#define SCVX_QP_RESERVE_HALF 2
+
+/* The two order lists of scvx_qp_solve_batched_split from the previous solve's IPM iteration counts (one workgroup,
+ * deterministic, no host synchronisation; csrc/qp_dispatch.hip).  iters device int32 [N], clamped to [0, max_iter].
+ * All agents sorted by descending count, ties by ascending index (a stable counting sort): the first n_tail of them go to
+ * order_tail [T], the rest to order_bulk [N], in that order; the unused entries of both lists are SCVX_QP_ORDER_SKIP.
+ * n_tail = min(T, #{iters >= thr}), and with short_per_tail > 0 also at most #{iters < thr} / short_per_tail: every
+ * running tail workgroup displaces that many bulk workgroups into a second round (three with
+ * SCVX_QP_RESERVE_WHOLE on a compute unit of four, one with _HALF), which pays only while those are short solves -- a
+ * batch whose agents all reach thr gets no tail.  short_per_tail = 0: no such limit.  T = 0 (order_tail may be NULL):
+ * order_bulk is the whole sort, the longest-first order of scvx_qp_solve_batched_ordered.  Limits: 0 <= T <= N,
+ * 1 <= max_iter <= 1023, and ceil(N / 64) * (max_iter + 1) <= 12288 (the count table in LDS), else SCVX_EUNSUPPORTED. */
+int scvx_qp_dispatch_select(int N, const int32_t* iters, int thr, int T, int short_per_tail, int max_iter,
+                            int32_t* order_tail, int32_t* order_bulk, void* stream);
+
+/* scvx_qp_solve_batched_ordered as two launches of the same kernel (qp_capi.hip): the agents of order_tail
+ * (device int32 [T]) on a library-owned non-blocking side stream, submitted first and with the LDS request of
+ * `reserve` (the kernel does not use the extra LDS), so each of them has a compute unit to itself or shares it with
+ * one workgroup instead of three; the agents of order_bulk (device int32 [N]) on `stream` with the usual request.
+ * Between them the two lists name every agent once (scvx_qp_dispatch_select); the rest is SCVX_QP_ORDER_SKIP.  The side
+ * stream waits for everything enqueued on `stream` before the call, and `stream` waits for both launches after it (two
+ * events, no host synchronisation).  Not to be called under stream capture.  Every output is what the single launch
+ * writes, bit for bit: the same instruction stream runs on the same data.  A runtime-compiled class
+ * (SCVX_MODEL_RUNTIME) and a refused tail launch solve every agent in one launch instead. */
+int scvx_qp_solve_batched_split(const scvx_qp_template* tpl, int N, const double* disc, const double* sigma,
+                                const double* Xref, const double* Uref, const double* x_init, const double* x_final,
+                                const double* tr, const double* coll_rows, const int32_t* coll_count, double* X,
+                                double* U, double* slack_coll, double* nu, double* obj, int32_t* status,
+                                int32_t* iters, const int32_t* warm, const int32_t* order_bulk,
+                                const int32_t* order_tail, int T, int reserve, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* Bytes of caller-owned device scratch scvx_qp_solve_batched needs for N agents. */
 size_t scvx_qp_workspace_bytes(const scvx_qp_template* tpl, int N);
