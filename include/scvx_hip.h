@@ -296,7 +296,10 @@ int scvx_collision_rows_indexed(int K, int pos_dim, int n_x, int N_total, const 
  * local agent i, node t < K-1 and every j != i of X_all (the linearisation point):
  *     v = (2R - |pbar_i - pbar_j|) - g_ij' (p_t - pbar_i) - S_t,   g_ij = (pbar_i - pbar_j)/|.|
  * with p_t = X_new[i][t][0:pos_dim], S_t = slack[i][t].  Outputs viol [N_local][K] = #{j : v > tol}
- * and vmax [N_local][K] = max_j v (0 at t = K-1).  A culled solve (j_max < N_total-1) is the
+ * and vmax [N_local][K] = max_j v (0 at t = K-1).  A coincident neighbour's row is NaN (the reference's
+ * 0/0): it is counted in viol and makes vmax NaN.  A fleet of one (N_total = 1) has no row: viol = 0 and
+ * vmax = -1e300, the maximum's start value, below every row value (finite, so a reduction over agents
+ * stays finite).  A culled solve (j_max < N_total-1) is the
  * reference's solution iff no row is violated: the culled problem is a relaxation of the full one.
  */
 int scvx_collision_check_batched(int K, int pos_dim, int n_x, int N_total, const double* X_all, int i0,

@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+import collision_ref
 from oracle import foh_oracle, problems as pb, qp_cpu
 
 N_TOTAL, K, ITERS = 6, 20, 3
@@ -29,18 +30,20 @@ class OracleBackend:
         return self.collision_rows_indexed(X_all, torch.arange(i0, i0 + n_local), R, j_max, pos_dim, cull, rows, count)
 
     def collision_rows_indexed(self, X_all, idx, R, j_max, pos_dim, cull, rows, count):
-        """The j_max nearest neighbours' rows per node (the kernel's selection: largest 2R - |d|), kept in
-        neighbour-index order."""
+        """The j_max nearest neighbours' rows per node (the kernel's selection: largest 2R - |d|) among those the
+        plain reference (tests/collision_ref.py) finds eligible -- j != i and, with cull > 0, |d| < cull strictly --
+        kept in neighbour-index order."""
         Xa = X_all.numpy()
         trajs = [Xa[i] for i in range(Xa.shape[0])]
         rows.zero_(); count.zero_()
         for a, gi in enumerate(idx.tolist()):
             rr = pb.collision_rows(trajs, gi, R, pos_dim)
-            others = [j for j in range(Xa.shape[0]) if j != gi]
             for t in range(Xa.shape[1] - 1):
-                dist = [np.linalg.norm(Xa[gi, t, :pos_dim] - Xa[j, t, :pos_dim]) for j in others]
-                keep = sorted(sorted(range(len(others)), key=lambda k: dist[k])[:j_max])
-                rows[a, t, :len(keep)] = torch.from_numpy(rr[t][keep])
+                ref = collision_ref.rows_ref(Xa, gi, t, R, pos_dim, cull)
+                near = ref.idx[np.argsort(ref.d2, kind="stable")[:j_max]]
+                keep = sorted(j - (j > gi) for j in near.tolist())       # rr leaves gi out
+                if keep:
+                    rows[a, t, :len(keep)] = torch.from_numpy(rr[t][keep])
                 count[a, t] = len(keep)
         return rows, count
 
