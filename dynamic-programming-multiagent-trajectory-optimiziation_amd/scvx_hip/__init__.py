@@ -114,6 +114,16 @@ def _auto_nsub(model, sigma, K):
     return default_nsub(model, float(sigma.max().item()) if sigma.numel() else 0.0, K)
 
 
+def _nsub(who, nsub, default):
+    """The RK4 substep count of a launch: `nsub` as given (an error below 1; 0 is no request for the default), or for
+    None what default() returns (a call, since _auto_nsub may read the device)."""
+    if nsub is None:
+        return int(default())
+    if int(nsub) < 1:
+        raise ValueError(f"{who}: nsub >= 1 required, got {nsub}")
+    return int(nsub)
+
+
 def disc_stride(model):
     n, m = model_dims(model)
     return n * (n + 2 * m + 2)
@@ -164,12 +174,16 @@ def foh_batched(model, X, U, sigma, nsub=None, params=None, out=None, stream=Non
     for the batch's longest interval (for the quadrotor this reads max(sigma) on the host; pass nsub to avoid it)."""
     torch = _torch()
     N, K, n, m = _check_xus("foh_batched", model, X, U, sigma)
+    if K < 2:
+        raise ValueError("foh_batched: K >= 2 required")
+    nsub = _nsub("foh_batched", nsub, lambda: _auto_nsub(model, sigma, K))
     if out is None:
         out = torch.empty((N, K - 1, disc_stride(model)), dtype=torch.float64, device=X.device)
+    if N == 0:      # nothing to launch (an empty tensor has no device pointer for the C-ABI's null checks)
+        return out
     keep, pp = _params(model, params)
     rc = lib().scvx_foh_batched(MODEL_IDS[model], pp, K, N, _dev(X, name="X"), _dev(U, name="U"),
-                                _dev(sigma, name="sigma"), int(nsub or _auto_nsub(model, sigma, K)),
-                                _dev(out, name="out"), _stream(stream))
+                                _dev(sigma, name="sigma"), nsub, _dev(out, name="out"), _stream(stream))
     check(rc, "scvx_foh_batched")
     return out
 
@@ -178,11 +192,16 @@ def integrate_nonlinear(model, X, U, sigma, piecewise, nsub=16, params=None, out
     """Batched FirstOrderHold.integrate_nonlinear_piecewise (piecewise=True) / _full (False)."""
     torch = _torch()
     N, K, n, m = _check_xus("integrate_nonlinear", model, X, U, sigma)
+    if K < 2:
+        raise ValueError("integrate_nonlinear: K >= 2 required")
+    nsub = _nsub("integrate_nonlinear", nsub, lambda: 16)
     if out is None:
         out = torch.empty_like(X)
+    if N == 0:
+        return out
     keep, pp = _params(model, params)
     rc = lib().scvx_integrate_nonlinear_batched(MODEL_IDS[model], pp, K, N, _dev(X, name="X"), _dev(U, name="U"),
-                                                _dev(sigma, name="sigma"), int(nsub), int(bool(piecewise)),
+                                                _dev(sigma, name="sigma"), nsub, int(bool(piecewise)),
                                                 _dev(out, name="out"), _stream(stream))
     check(rc, "scvx_integrate_nonlinear_batched")
     return out
@@ -782,11 +801,11 @@ def rollout_dense(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=None,
     if not 1 <= S <= 16 or not 1 <= pos_dim <= min(3, n):
         raise ValueError(f"rollout_dense: 1 <= S <= 16 and 1 <= pos_dim <= {min(3, n)} required, got S={S}, "
                          f"pos_dim={pos_dim}")
-    nsub = int(nsub or _auto_nsub(model, sigma, K))
-    if nsub < 1:
-        raise ValueError("rollout_dense: nsub >= 1 required")
+    nsub = _nsub("rollout_dense", nsub, lambda: _auto_nsub(model, sigma, K))
     P = torch.empty((N, K - 1, S + 1, 3), dtype=torch.float64, device=X.device)
     L = torch.empty((N, K - 1), dtype=torch.float64, device=X.device)
+    if N == 0:
+        return P, L
     keep, pp = _params(model, params)
     rc = lib().scvx_rollout_dense_batched(MODEL_IDS[model], pp, K, N, _dev(X, name="X"), _dev(U, name="U"),
                                           _dev(sigma, name="sigma"), S, -(-nsub // S), pos_dim, _dev(P, name="P"),

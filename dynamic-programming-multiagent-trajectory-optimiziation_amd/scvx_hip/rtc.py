@@ -163,28 +163,37 @@ class DeviceModel:
     def foh(self, X, U, sigma, nsub=None, params=None, out=None, stream=None):
         """Batched FirstOrderHold.calculate_discretization: X (N,K,n), U (N,K,m), sigma (N,) float64
         device tensors -> disc (N, K-1, n(n+2m+2)) (layout of scvx_hip.foh_batched)."""
-        from . import _check_xus, _dev, _stream, _torch
+        from . import _check_xus, _dev, _nsub, _stream, _torch
         torch = _torch()
         N, K, n, m = _check_xus("DeviceModel.foh", self, X, U, sigma)
+        if K < 2:
+            raise ValueError("DeviceModel.foh: K >= 2 required")
+        nsub = _nsub("DeviceModel.foh", nsub, lambda: self.nsub)
         if out is None:
             out = torch.empty((N, K - 1, n * (n + 2 * m + 2)), dtype=torch.float64, device=X.device)
+        if N == 0:
+            return out
         pa, npar = self._pp(params)
         rc = lib().scvx_rtc_foh_batched(self._h.ptr, pa.ctypes.data, npar, K, N, _dev(X, name="X"), _dev(U, name="U"),
-                                        _dev(sigma, name="sigma"), int(nsub or self.nsub), _dev(out, name="out"),
-                                        _stream(stream))
+                                        _dev(sigma, name="sigma"), nsub, _dev(out, name="out"), _stream(stream))
         check(rc, "scvx_rtc_foh_batched")
         return out
 
     def integrate_nonlinear(self, X, U, sigma, piecewise, nsub=16, params=None, out=None, stream=None):
         """Batched integrate_nonlinear_piecewise (piecewise=True) / integrate_nonlinear_full (False)."""
-        from . import _check_xus, _dev, _stream, _torch
+        from . import _check_xus, _dev, _nsub, _stream, _torch
         torch = _torch()
         N, K, n, _ = _check_xus("DeviceModel.integrate_nonlinear", self, X, U, sigma)
+        if K < 2:
+            raise ValueError("DeviceModel.integrate_nonlinear: K >= 2 required")
+        nsub = _nsub("DeviceModel.integrate_nonlinear", nsub, lambda: 16)
         if out is None:
             out = torch.empty((N, K, n), dtype=torch.float64, device=X.device)
+        if N == 0:
+            return out
         pa, npar = self._pp(params)
         rc = lib().scvx_rtc_integrate_nonlinear_batched(self._h.ptr, pa.ctypes.data, npar, K, N, _dev(X, name="X"),
-                                                        _dev(U, name="U"), _dev(sigma, name="sigma"), int(nsub),
+                                                        _dev(U, name="U"), _dev(sigma, name="sigma"), nsub,
                                                         int(bool(piecewise)), _dev(out, name="out"), _stream(stream))
         check(rc, "scvx_rtc_integrate_nonlinear_batched")
         return out

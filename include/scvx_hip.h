@@ -63,7 +63,8 @@ const char* scvx_last_error(void);
  * (SCvx/discretization/first_order_hold.py:52-87) for N agents in one launch.
  *   X [N][K][n], U [N][K][m], sigma [N]  ->  out [N][K-1][n*(n+2m+2)]
  * nsub = RK4 substeps per interval (1 is exact for the double integrator).
- * params: model parameters (quadrotor: mass, g, Jx, Jy, Jz) or NULL for defaults.
+ * params: for the quadrotor five doubles in host memory, mass, g, Jx, Jy, Jz, or NULL for the defaults
+ * (1, 9.81, 0.02, 0.02, 0.04); ignored (may be NULL) for the other models.
  */
 int scvx_foh_batched(int model_id, const double* params, int K, int N, const double* X, const double* U,
                      const double* sigma, int nsub, double* out, void* stream);
