@@ -3,7 +3,8 @@
 Same functions and arguments, numpy in and numpy out: `min_inter_agent_distance` (:10-31),
 `min_agent_obstacle_distance` (:34-62), `compute_intersample_clearance` (:64-104).  The pairwise and
 obstacle minima run in scvx_pair_min_distance_batched / scvx_obstacle_min_distance_batched instead of the
-reference's Python double loop; the dense roll-outs in scvx_rollout_dense_batched.
+reference's Python double loop; the dense roll-outs in scvx_rollout_dense_batched, or for a model that is not built
+in, in its runtime-compiled form (scvx_hip.rtc.DeviceModel, scvx_rtc_rollout_dense_batched).
 
 Added here (no reference counterpart): `min_inter_agent_separation_continuous`, the closest approach of
 any two agents BETWEEN the nodes as well as at them (scvx_hip.fleet_separation), and
@@ -15,7 +16,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 import scvx_hip
-from SCvx.discretization.first_order_hold import FirstOrderHold, builtin_model
+from SCvx.discretization.first_order_hold import FirstOrderHold, device_model
 
 
 def _stack(X_list, device):
@@ -53,12 +54,14 @@ def compute_intersample_clearance(X: np.ndarray, U: np.ndarray, foh, obs_center:
 
     The roll-outs are scvx_hip.rollout_dense calls on chunks of at most 16 samples (its limit): chunk c of every
     segment starts from the segment's state at its first sample (one integrate_nonlinear roll-out from the node)
-    and is sampled at the trajectory's own FOH input restricted to the chunk."""
+    and is sampled at the trajectory's own FOH input restricted to the chunk.  Any model: a user model runs its
+    DeviceModel's integrate_nonlinear and rollout_dense."""
     import torch
     X, U = np.asarray(X, float), np.asarray(U, float)
-    model = builtin_model(foh.model, "compute_intersample_clearance")
+    model = getattr(foh, "_name", None) or device_model(foh.model)
     dev = getattr(foh, "_device", "cuda")
     params = getattr(foh.model, "scvx_params", None)
+    user = not isinstance(model, str)   # a DeviceModel
     K, res = X.shape[1], int(resolution)
     c = np.asarray(obs_center, float).reshape(-1)
     pd = c.size
@@ -78,8 +81,9 @@ def compute_intersample_clearance(X: np.ndarray, U: np.ndarray, foh, obs_center:
         ua, ub = u0 + t0 * (u1 - u0), u0 + t1 * (u1 - u0)
         xs = x0
         if i0:   # the segments' states at t0: a one-interval roll-out over [0, t0 dt] whose end input is u(t0)
-            out = scvx_hip.integrate_nonlinear(model, dev_t(np.stack([x0, x0], 1)), dev_t(np.stack([u0, ua], 1)),
-                                               dev_t(np.full(K - 1, t0 * dtp)), True, nsub=nsub, params=params)
+            roll = model.integrate_nonlinear if user else (lambda *a, **kw: scvx_hip.integrate_nonlinear(model, *a, **kw))
+            out = roll(dev_t(np.stack([x0, x0], 1)), dev_t(np.stack([u0, ua], 1)), dev_t(np.full(K - 1, t0 * dtp)),
+                       True, nsub=nsub, params=params)
             xs = out[:, 1].cpu().numpy()
         P, _ = scvx_hip.rollout_dense(model, dev_t(np.stack([xs, xs], 1)), dev_t(np.stack([ua, ub], 1)),
                                       dev_t(np.full(K - 1, (t1 - t0) * dtp)), S=cnt, nsub=nsub, pos_dim=pd,
@@ -93,74 +97,80 @@ def compute_intersample_clearance(X: np.ndarray, U: np.ndarray, foh, obs_center:
     return tau_cont, h_cont, tau_disc, h_disc
 
 
-def _device_model(foh_or_model, who, device):
-    """(built-in model name, params, device) of a FirstOrderHold, a model object or a built-in device model name."""
-    if isinstance(foh_or_model, FirstOrderHold):
-        return (builtin_model(foh_or_model.model, who), getattr(foh_or_model.model, "scvx_params", None),
+def _device_model(foh_or_model, device):
+    """(device model, params, device) of a FirstOrderHold, a model object, a built-in device model name or a
+    scvx_hip.rtc.DeviceModel.  The device model is a built-in name or a DeviceModel (a FirstOrderHold's own; a model
+    object's `scvx_device_model`, else its get_equations() re-traced: first_order_hold.device_model)."""
+    if isinstance(foh_or_model, FirstOrderHold):   # resolved at its construction
+        return (foh_or_model._name, getattr(foh_or_model.model, "scvx_params", None),
                 getattr(foh_or_model, "_device", device))
     if isinstance(foh_or_model, str):
         return foh_or_model, None, device
-    return builtin_model(foh_or_model, who), getattr(foh_or_model, "scvx_params", None), device
+    if callable(getattr(foh_or_model, "rollout_dense", None)):   # a DeviceModel: its own launch parameters
+        return foh_or_model, None, device
+    return device_model(foh_or_model), getattr(foh_or_model, "scvx_params", None), device
+
+
+def _rollout_nsub(model, sig, K):
+    """RK4 substeps of the continuous-time functions: exact at the default for the integrators, else at least 16
+    (scvx_hip.integrate_nonlinear's default) and at least the FOH's count for the longest interval."""
+    if isinstance(model, str) and model in ("di", "si"):
+        return None
+    return max(16, scvx_hip.default_nsub(model, float(sig.max()), K))
 
 
 def min_agent_obstacle_clearance_continuous(X_list: List[np.ndarray], U_list: List[np.ndarray], foh_or_model, sigma,
                                             obstacles: Sequence, robot_radius: float, S: int = 8,
-                                            device="cuda") -> Tuple[float, np.ndarray]:
+                                            device="cuda", pos_dim=None) -> Tuple[float, np.ndarray]:
     """min_agent_obstacle_distance in continuous time (not in the reference): (d_min_global, d_mat) with
     d_mat[i, j] = min over the whole trajectory, between the nodes as well as at them, of
     ||p_i - c_j|| - (robot_radius + r_j); d_min_global its minimum (negative when penetrating).
 
-    X_list / U_list: per agent (n, K) / (m, K); foh_or_model: a FirstOrderHold, a model object or a built-in
-    device model name; sigma: one horizon for all agents or one per agent; obstacles [(centre, radius)], centres
-    of up to 3 coordinates.
+    X_list / U_list: per agent (n, K) / (m, K); foh_or_model: a FirstOrderHold, a model object, a built-in
+    device model name or a scvx_hip.rtc.DeviceModel; sigma: one horizon for all agents or one per agent; obstacles
+    [(centre, radius)], centres of up to 3 coordinates.  pos_dim: the leading states that are positions -- required
+    for a model that is not built in, scvx_hip.rollout_dense's default otherwise.
 
     Accuracy: exact for the piecewise-linear interpolant of S samples per segment; within max ||r''|| h^2 / 8 of
     the continuous minimum, h = 1 / ((K-1) S) in normalised time and r = p - c (double integrator:
     ||r''|| <= max(sigma^2 ||u||)).  Never above min_agent_obstacle_distance's matrix: the nodes are samples."""
     import torch
     who = "min_agent_obstacle_clearance_continuous"
-    model, params, device = _device_model(foh_or_model, who, device)
+    model, params, device = _device_model(foh_or_model, device)
     N = len(X_list)
     if len(U_list) != N:
         raise ValueError(f"{who}: X_list and U_list must have the same length")
     sig = np.broadcast_to(np.asarray(sigma, float), (N,)).copy()
     K = np.asarray(X_list[0]).shape[1]
-    nsub = max(16, scvx_hip.default_nsub(model, float(sig.max()), K)) if model not in ("di", "si") else None
     out = scvx_hip.fleet_obstacle_clearance(model, _stack(X_list, device), _stack(U_list, device),
                                             torch.as_tensor(sig, device=device), list(obstacles), robot_radius, S=S,
-                                            nsub=nsub, params=params)
+                                            nsub=_rollout_nsub(model, sig, K), pos_dim=pos_dim, params=params)
     return out["min"], out["D"].cpu().numpy()
 
 
 def min_inter_agent_separation_continuous(X_list: List[np.ndarray], U_list: List[np.ndarray], foh_or_model, sigma,
-                                          S: int = 8, device="cuda"):
+                                          S: int = 8, device="cuda", pos_dim=None):
     """Closest approach of any two agents in continuous time (not in the reference): (d_min_global, d_seg, info).
 
-    X_list / U_list: per agent (n, K) / (m, K); foh_or_model: a FirstOrderHold, a model object or a built-in
-    device model name; sigma: one horizon for all agents or one per agent.  Agents are compared at equal
-    normalised time.  d_seg (N, K-1): per agent and segment the minimum distance to any other agent over the
-    segment; info: j (N, K-1) the other agent, tau (N, K-1) the position in the segment where it occurs,
+    X_list / U_list: per agent (n, K) / (m, K); foh_or_model: a FirstOrderHold, a model object, a built-in
+    device model name or a scvx_hip.rtc.DeviceModel; sigma: one horizon for all agents or one per agent; pos_dim: the
+    leading states that are positions -- required for a model that is not built in, scvx_hip.rollout_dense's default
+    otherwise.  Agents are compared at equal normalised time.  d_seg (N, K-1): per agent and segment the minimum
+    distance to any other agent over the segment; info: j (N, K-1) the other agent, tau (N, K-1) the position in the segment where it occurs,
     argmin = (i, j, k, tau) of d_min_global.
 
     Accuracy: exact for the piecewise-linear interpolant of S samples per segment; within max ||r''|| h^2 / 8 of
     the continuous minimum, h = 1 / ((K-1) S) in normalised time and r the relative position (double integrator:
     ||r''|| <= 2 max(sigma^2 ||u||))."""
     import torch
-    if isinstance(foh_or_model, FirstOrderHold):
-        model = builtin_model(foh_or_model.model, "min_inter_agent_separation_continuous")
-        params, device = getattr(foh_or_model.model, "scvx_params", None), getattr(foh_or_model, "_device", device)
-    elif isinstance(foh_or_model, str):
-        model, params = foh_or_model, None
-    else:
-        model = builtin_model(foh_or_model, "min_inter_agent_separation_continuous")
-        params = getattr(foh_or_model, "scvx_params", None)
+    model, params, device = _device_model(foh_or_model, device)
     N = len(X_list)
     if len(U_list) != N:
         raise ValueError("min_inter_agent_separation_continuous: X_list and U_list must have the same length")
     sig = np.broadcast_to(np.asarray(sigma, float), (N,)).copy()
     K = np.asarray(X_list[0]).shape[1]
-    nsub = max(16, scvx_hip.default_nsub(model, float(sig.max()), K)) if model not in ("di", "si") else None
     out = scvx_hip.fleet_separation(model, _stack(X_list, device), _stack(U_list, device),
-                                    torch.as_tensor(sig, device=device), S=S, nsub=nsub, params=params)
+                                    torch.as_tensor(sig, device=device), S=S, nsub=_rollout_nsub(model, sig, K),
+                                    pos_dim=pos_dim, params=params)
     info = dict(j=out["j"].cpu().numpy(), tau=out["tau"].cpu().numpy(), argmin=out["argmin"])
     return out["min"], out["sep"].cpu().numpy(), info

@@ -1,4 +1,4 @@
-// FOH and nonlinear roll-out kernel bodies and the roll-outs' one RK4 state step (rk4_step), templated on the model
+// FOH, nonlinear and dense roll-out kernel bodies and the roll-outs' one RK4 state step (rk4_step), templated on the model
 // (gfx950, float64).
 //
 // Shared by the built-in models (csrc/foh.hip: compiled with the library) and by runtime-compiled
@@ -155,7 +155,7 @@ __device__ __forceinline__ void foh_body(const double* __restrict__ X, const dou
 }
 
 // One classical RK4 step of x' = f(x, u0 + (t/T) du) from time t, step h, in place: the state step of every nonlinear
-// roll-out -- nonlinear_body below, rollout_dense_kernel (separation.hip), the h() of intersample_body.hpp.  The
+// roll-out -- nonlinear_body and rollout_dense_body below, the h() of intersample_body.hpp.  The
 // caller owns its expressions for t and h; T is the length of the interval the input is interpolated over.
 template <class Mdl>
 __device__ __forceinline__ void rk4_step(double* x, double t, double h, double T, const double* u0, const double* du,
@@ -214,5 +214,68 @@ __device__ __forceinline__ void nonlinear_body(const double* __restrict__ X, con
         for (int i = 0; i < n; ++i) Xout[(agent * K + k + 1) * n + i] = x[i];
     }
 }
+
+// Dense samples of every segment's nonlinear roll-out: one lane per (agent, segment), restart at X[:,k], FOH input
+// u_k + tau/T (u_{k+1} - u_k), T = sigma/(K-1) (nonlinear_body's piecewise roll-out), sampled every `sub` RK4 steps.
+// P (N,K-1,S+1,3): the first pd states (zeros past pd; pd <= min(3, Mdl::N), rollout_dense_check); L (N,K-1): the
+// polyline length of those samples.  The body of rollout_dense_kernel (separation.hip) and of a user model's
+// scvx_rtc_rollout_dense (foh_rtc.hip).
+template <class Mdl>
+__device__ __forceinline__ void rollout_dense_body(const double* __restrict__ X, const double* __restrict__ U,
+                                                   const double* __restrict__ sigma, double* __restrict__ P,
+                                                   double* __restrict__ L, int K, int N, int S, int sub, int pd,
+                                                   const ModelParams& Pm) {
+    constexpr int n = Mdl::N, m = Mdl::M;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= (long long)N * (K - 1)) return;
+    const long long agent = tid / (K - 1);
+    const int k = (int)(tid % (K - 1));
+    const double T = sigma[agent] / (K - 1), h = T / ((double)S * sub);
+    // the samples read x[d] for d < 3: a model with fewer states gets the array padded with zeros (compile time; the
+    // integrator touches the first n entries only), so that the sample loops below are the same code for every n
+    constexpr int nx = n < 3 ? 3 : n;
+    double x[nx], u0[m], du[m];
+#pragma unroll
+    for (int i = 0; i < n; ++i) x[i] = X[(agent * K + k) * n + i];
+#pragma unroll
+    for (int i = n; i < nx; ++i) x[i] = 0.0;
+    const double* u0p = U + (agent * K + k) * m;
+#pragma unroll
+    for (int j = 0; j < m; ++j) { u0[j] = u0p[j]; du[j] = u0p[m + j] - u0[j]; }
+    double* out = P + tid * (long long)(S + 1) * 3;
+    double prev[3], len = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        prev[d] = d < pd ? x[d] : 0.0;
+        out[d] = prev[d];
+    }
+    for (int s = 1; s <= S; ++s) {
+        for (int i = 0; i < sub; ++i) rk4_step<Mdl>(x, ((long long)(s - 1) * sub + i) * h, h, T, u0, du, Pm);
+        double l2 = 0.0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const double p = d < pd ? x[d] : 0.0;
+            l2 += (p - prev[d]) * (p - prev[d]);
+            prev[d] = p;
+            out[s * 3 + d] = p;
+        }
+        len += sqrt(l2);
+    }
+    L[tid] = len;
+}
+
+#ifndef __HIPCC_RTC__
+// Host-side argument check of the dense roll-out's entry points (built-in and runtime-compiled): nullptr, or what
+// is wrong.  n_x: the model's state dimension (0: not known yet, checked by the launcher).
+inline const char* rollout_dense_check(int K, int N, int S, int sub, int pos_dim, int n_x, const void* X,
+                                       const void* U, const void* sigma, const void* P, const void* L) {
+    if (K < 2 || N < 0) return "rollout_dense: K >= 2 and N >= 0 required";
+    if (S < 1 || S > 16 || sub < 1) return "rollout_dense: 1 <= S <= 16 and sub >= 1 required";
+    if (pos_dim < 1 || pos_dim > 3) return "rollout_dense: 1 <= pos_dim <= 3 required";
+    if (n_x > 0 && pos_dim > n_x) return "rollout_dense: pos_dim exceeds the model's state dimension";
+    if (!X || !U || !sigma || !P || !L) return "rollout_dense: null buffer";
+    return nullptr;
+}
+#endif
 
 }  // namespace scvx

@@ -5,7 +5,8 @@
 // are compiled into the library; a user model arrives as C expressions (include/scvx_hip.h), is
 // wrapped into a model struct with the csrc/models.hpp contract and compiled by hipRTC together with
 // csrc/foh_body.hpp -- the integrator the built-in models use, embedded in the library as text at build time --
-// into two extern "C" kernels.  The Jacobians are applied as sparse matrix-vector products: entries
+// into its extern "C" kernels: the FOH, the nonlinear roll-out, the dense roll-out and (n_x <= SCVX_IS_MAX_STATE) the
+// inter-sample scan.  The Jacobians are applied as sparse matrix-vector products: entries
 // given as structural zeros generate no code.
 //
 // Compile at create (host only, no GPU needed); load the code object per device at the first
@@ -89,6 +90,11 @@ std::string generate(int n, int m, const char* const* f, const char* const* A, c
     s += "extern \"C\" __global__ __launch_bounds__(256) void scvx_rtc_nonlinear(const double* X, const double* U,\n"
          "        const double* sigma, double* Xout, int K, int N, int nsub, int piecewise, scvx::ModelParams P) {\n"
          "    scvx::nonlinear_body<UserModel>(X, U, sigma, Xout, K, N, nsub, piecewise, P);\n}\n";
+    // the dense roll-out under the fleet scans and the continuous-time rows: 64 lanes, one per (agent, segment), as
+    // rollout_dense_kernel (separation.hip)
+    s += "extern \"C\" __global__ __launch_bounds__(64) void scvx_rtc_rollout_dense(const double* X, const double* U,\n"
+         "        const double* sigma, double* P, double* L, int K, int N, int S, int sub, int pd, scvx::ModelParams Pm) {\n"
+         "    scvx::rollout_dense_body<UserModel>(X, U, sigma, P, L, K, N, S, sub, pd, Pm);\n}\n";
     if (n <= SCVX_IS_MAX_STATE) {   // the inter-sample scan (csrc/intersample_body.hpp) on this model's f
         s += "#include \"intersample_body.hpp\"\n";
         s += "extern \"C\" __global__ __launch_bounds__(256) void scvx_rtc_intersample(scvx::ISArgs a) {\n"
@@ -177,6 +183,20 @@ extern "C" int scvx_rtc_integrate_nonlinear_batched(const scvx_rtc_model* model,
     void* args[] = {(void*)&X, (void*)&U, (void*)&sigma, (void*)&Xout, (void*)&K, (void*)&N, (void*)&nsub,
                     (void*)&piecewise, (void*)&P};
     return launch(model, "rtc nl", "scvx_rtc_nonlinear", total, piecewise ? 256 : 64, args, stream);
+}
+
+extern "C" int scvx_rtc_rollout_dense_batched(const scvx_rtc_model* model, const double* params, int n_params, int K,
+                                              int N, const double* X, const double* U, const double* sigma, int S,
+                                              int sub, int pos_dim, double* P, double* L, void* stream) {
+    if (!model || model->code.empty()) return scvx::set_error(SCVX_EINVAL, "rtc rollout_dense: no compiled model");
+    if (const char* bad = scvx::rollout_dense_check(K, N, S, sub, pos_dim, model->n, X, U, sigma, P, L))
+        return scvx::set_error(SCVX_EINVAL, bad);
+    scvx::ModelParams Pm;
+    if (int rc = params_of(params, n_params, &Pm)) return rc;
+    if (N == 0) return SCVX_OK;
+    void* args[] = {(void*)&X, (void*)&U, (void*)&sigma, (void*)&P, (void*)&L, (void*)&K, (void*)&N, (void*)&S,
+                    (void*)&sub, (void*)&pos_dim, (void*)&Pm};
+    return launch(model, "rtc rollout_dense", "scvx_rtc_rollout_dense", (long long)N * (K - 1), 64, args, stream);
 }
 
 extern "C" int scvx_rtc_intersample_batched(const scvx_rtc_model* model, const double* params, int n_params,

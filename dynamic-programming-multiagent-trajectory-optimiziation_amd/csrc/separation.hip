@@ -30,46 +30,13 @@
 
 namespace scvx {
 
-// one lane per (agent, segment): restart at X[:,k], FOH input u_k + tau/T (u_{k+1} - u_k), T = sigma/(K-1)
-// (nonlinear_body's piecewise roll-out, foh_body.hpp), sampled every `sub` RK4 steps (rk4_step)
+// one lane per (agent, segment): rollout_dense_body (foh_body.hpp), shared with the runtime-compiled user models
 template <class Mdl>
 __global__ __launch_bounds__(64) void rollout_dense_kernel(const double* __restrict__ X, const double* __restrict__ U,
                                                            const double* __restrict__ sigma, double* __restrict__ P,
                                                            double* __restrict__ L, int K, int N, int S, int sub,
                                                            int pd, ModelParams Pm) {
-    constexpr int n = Mdl::N, m = Mdl::M;
-    static_assert(n >= 3, "the samples are the first pos_dim <= 3 states");
-    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= (long long)N * (K - 1)) return;
-    const long long agent = tid / (K - 1);
-    const int k = (int)(tid % (K - 1));
-    const double T = sigma[agent] / (K - 1), h = T / ((double)S * sub);
-    double x[n], u0[m], du[m];
-#pragma unroll
-    for (int i = 0; i < n; ++i) x[i] = X[(agent * K + k) * n + i];
-    const double* u0p = U + (agent * K + k) * m;
-#pragma unroll
-    for (int j = 0; j < m; ++j) { u0[j] = u0p[j]; du[j] = u0p[m + j] - u0[j]; }
-    double* out = P + tid * (long long)(S + 1) * 3;
-    double prev[3], len = 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        prev[d] = d < pd ? x[d] : 0.0;
-        out[d] = prev[d];
-    }
-    for (int s = 1; s <= S; ++s) {
-        for (int i = 0; i < sub; ++i) rk4_step<Mdl>(x, ((long long)(s - 1) * sub + i) * h, h, T, u0, du, Pm);
-        double l2 = 0.0;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const double p = d < pd ? x[d] : 0.0;
-            l2 += (p - prev[d]) * (p - prev[d]);
-            prev[d] = p;
-            out[s * 3 + d] = p;
-        }
-        len += sqrt(l2);
-    }
-    L[tid] = len;
+    rollout_dense_body<Mdl>(X, U, sigma, P, L, K, N, S, sub, pd, Pm);
 }
 
 template <int S, bool PRUNE>
@@ -230,7 +197,8 @@ __global__ __launch_bounds__(256) void obstacle_min_kernel(int K, int nx, int N,
 template <class Mdl>
 static int launch_rollout_dense(const double* X, const double* U, const double* sigma, double* P, double* L, int K,
                                 int N, int S, int sub, int pd, const ModelParams& Pm, hipStream_t st) {
-    if (pd > Mdl::N) return set_error(SCVX_EINVAL, "rollout_dense: pos_dim exceeds the model's state dimension");
+    if (const char* bad = rollout_dense_check(K, N, S, sub, pd, Mdl::N, X, U, sigma, P, L))
+        return set_error(SCVX_EINVAL, bad);
     if (N == 0) return SCVX_OK;
     const long long total = (long long)N * (K - 1);
     hipLaunchKernelGGL(rollout_dense_kernel<Mdl>, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, X, U, sigma, P,
@@ -258,10 +226,13 @@ using namespace scvx;
 extern "C" int scvx_rollout_dense_batched(int model_id, const double* params, int K, int N, const double* X,
                                           const double* U, const double* sigma, int S, int sub, int pos_dim, double* P,
                                           double* L, void* stream) {
-    if (K < 2 || N < 0 || S < 1 || S > 16 || sub < 1 || pos_dim < 1 || pos_dim > 3 || !X || !U || !sigma || !P || !L)
-        return set_error(SCVX_EINVAL, "rollout_dense: bad args");
+    // the rules that need no model first (n_x = 0), so that a bad argument is SCVX_EINVAL whatever the model id; the
+    // launcher repeats the check with the model's n_x
+    if (const char* bad = rollout_dense_check(K, N, S, sub, pos_dim, 0, X, U, sigma, P, L))
+        return set_error(SCVX_EINVAL, bad);
     if (model_id == SCVX_MODEL_RUNTIME)
-        return set_error(SCVX_EUNSUPPORTED, "rollout_dense: built-in models only (no runtime-compiled form)");
+        return set_error(SCVX_EUNSUPPORTED,
+                         "rollout_dense: a runtime-compiled model goes through scvx_rtc_rollout_dense_batched");
     const ModelParams Pm = model_params(model_id, params);
     return dispatch_model(model_id, "rollout_dense", [&](auto tag) {
         return launch_rollout_dense<typename decltype(tag)::type>(X, U, sigma, P, L, K, N, S, sub, pos_dim, Pm,

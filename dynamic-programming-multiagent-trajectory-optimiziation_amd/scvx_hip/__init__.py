@@ -783,24 +783,42 @@ def intersample_batched(model, X, U, sigma, obstacles, proj=None, dt=1.0, seg_dt
     return {k: v[:, :, :O] for k, v in out.items()}
 
 
+def _rollout_dense_args(who, model, X, U, sigma, S, pos_dim):
+    """The arguments of a dense roll-out, built-in (rollout_dense) or runtime-compiled (DeviceModel.rollout_dense),
+    checked before any device access -> (N, K, S, pos_dim).  pos_dim None: 2 for the unicycle, 3 for the other
+    built-in models; a user model has no default (which of its states are positions is the caller's knowledge: the
+    kinematic car's third state is a heading)."""
+    N, K, n, m = _check_xus(who, model, X, U, sigma)
+    if K < 2:
+        raise ValueError(f"{who}: K >= 2 required")
+    if pos_dim is None:
+        if not isinstance(model, str):
+            raise ValueError(f"{who}: pos_dim is required for a user model (the number of leading states that are "
+                             f"positions, 1 <= pos_dim <= {min(3, n)})")
+        pos_dim = 2 if model == "unicycle" else 3
+    S, pos_dim = int(S), int(pos_dim)
+    if not 1 <= S <= 16 or not 1 <= pos_dim <= min(3, n):
+        raise ValueError(f"{who}: 1 <= S <= 16 and 1 <= pos_dim <= {min(3, n)} required, got S={S}, "
+                         f"pos_dim={pos_dim}")
+    return N, K, S, pos_dim
+
+
 def rollout_dense(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=None, stream=None):
     """Dense samples of every segment's nonlinear roll-out (scvx_rollout_dense_batched): X (N,K,n), U (N,K,m),
     sigma (N,) float64 device tensors -> (P, L), P (N,K-1,S+1,3) the first pos_dim states at tau = s/S of each
     segment (zeros past pos_dim), L (N,K-1) the polyline length of those samples.  Restarts at every node, as
     integrate_nonlinear(piecewise=True).  RK4 with sub = ceil(nsub / S) steps between samples; nsub None:
     default_nsub for the batch's longest interval (exact for "di" / "si").  pos_dim None: 2 for the unicycle,
-    else 3.  Built-in models only."""
+    else 3.  model: a built-in name, or a scvx_hip.rtc.DeviceModel (any user model: its own rollout_dense, the same
+    kernel body on its runtime-compiled f; pos_dim is then required and nsub None means the model's nsub)."""
     torch = _torch()
     if not isinstance(model, str):
-        raise NotImplementedError("rollout_dense: compiled for the built-in models only (no runtime-compiled form)")
-    N, K, n, m = _check_xus("rollout_dense", model, X, U, sigma)
-    if K < 2:
-        raise ValueError("rollout_dense: K >= 2 required")
-    pos_dim = (2 if model == "unicycle" else 3) if pos_dim is None else int(pos_dim)
-    S = int(S)
-    if not 1 <= S <= 16 or not 1 <= pos_dim <= min(3, n):
-        raise ValueError(f"rollout_dense: 1 <= S <= 16 and 1 <= pos_dim <= {min(3, n)} required, got S={S}, "
-                         f"pos_dim={pos_dim}")
+        roll = getattr(model, "rollout_dense", None)
+        if roll is None:
+            raise NotImplementedError("rollout_dense: the model must be a built-in name or offer rollout_dense "
+                                      "(scvx_hip.rtc.DeviceModel)")
+        return roll(X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim, params=params, stream=stream)
+    N, K, S, pos_dim = _rollout_dense_args("rollout_dense", model, X, U, sigma, S, pos_dim)
     nsub = _nsub("rollout_dense", nsub, lambda: _auto_nsub(model, sigma, K))
     P = torch.empty((N, K - 1, S + 1, 3), dtype=torch.float64, device=X.device)
     L = torch.empty((N, K - 1), dtype=torch.float64, device=X.device)
@@ -857,7 +875,8 @@ def fleet_separation(model, X, U, sigma, S=8, nsub=None, pos_dim=None, params=No
     """rollout_dense + separation_scan of a whole fleet: how close any two agents come, between the nodes as
     well as at them.  Returns separation_scan's dict plus P, L (the samples), agent_min (N,) each agent's
     minimum over its segments, min (float) the fleet's minimum and argmin = (i, j, k, tau) where it occurs
-    (None for a single agent).  The accuracy statement of separation_scan applies; for the double integrator
+    (None for a single agent).  model: a built-in name or a DeviceModel (pos_dim required), as rollout_dense; the
+    scan reads only the samples.  The accuracy statement of separation_scan applies; for the double integrator
     ||r''|| <= 2 max(sigma^2 ||u||) in normalised time."""
     P, L = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim, params=params, stream=stream)
     out = separation_scan(P, L, 0, X.shape[0], stream=stream)
@@ -1007,7 +1026,8 @@ def fleet_obstacle_clearance(model, X, U, sigma, obstacles, robot_radius=0.0, S=
     comes to any obstacle, between the nodes as well as at them.  obstacles: [(centre, radius r_o)].  Returns clear
     (N,K-1,O) = dist - (r_o + robot_radius) per segment, tau (N,K-1,O) where in the segment it occurs, D (N,O) the
     minimum over the segments (the continuous-time form of obstacle_min_distance's matrix), agent_min (N,), min
-    (float) and argmin = (i, o, k, tau) where it occurs, plus P, L (the samples).  The accuracy statement of
+    (float) and argmin = (i, o, k, tau) where it occurs, plus P, L (the samples).  model: a built-in name or a
+    DeviceModel (pos_dim required), as rollout_dense.  The accuracy statement of
     separation_scan applies with r = p - c the position relative to the (fixed) centre; for the double integrator
     ||r''|| <= max(sigma^2 ||u||) in normalised time."""
     torch = _torch()

@@ -198,6 +198,26 @@ class DeviceModel:
         check(rc, "scvx_rtc_integrate_nonlinear_batched")
         return out
 
+    def rollout_dense(self, X, U, sigma, S=8, nsub=None, pos_dim=None, params=None, stream=None):
+        """scvx_hip.rollout_dense for this model (scvx_rtc_rollout_dense_batched): -> (P, L), P (N,K-1,S+1,3) the
+        first pos_dim states at tau = s/S of every segment's roll-out (zeros past pos_dim), L (N,K-1) the samples'
+        polyline length.  sub = ceil(nsub / S) RK4 steps between samples; nsub None: the model's nsub.  pos_dim is
+        required (1 <= pos_dim <= min(3, n_x)): which leading states are positions is not the model's to guess."""
+        from . import _dev, _nsub, _rollout_dense_args, _stream, _torch
+        torch = _torch()
+        N, K, S, pos_dim = _rollout_dense_args("DeviceModel.rollout_dense", self, X, U, sigma, S, pos_dim)
+        nsub = _nsub("DeviceModel.rollout_dense", nsub, lambda: self.nsub)
+        P = torch.empty((N, K - 1, S + 1, 3), dtype=torch.float64, device=X.device)
+        L = torch.empty((N, K - 1), dtype=torch.float64, device=X.device)
+        if N == 0:
+            return P, L
+        pa, npar = self._pp(params)
+        rc = lib().scvx_rtc_rollout_dense_batched(self._h.ptr, pa.ctypes.data, npar, K, N, _dev(X, name="X"),
+                                                  _dev(U, name="U"), _dev(sigma, name="sigma"), S, -(-nsub // S),
+                                                  pos_dim, _dev(P, name="P"), _dev(L, name="L"), _stream(stream))
+        check(rc, "scvx_rtc_rollout_dense_batched")
+        return P, L
+
     def unpack_disc(self, disc):
         """[..., K-1, n(n+2m+2)] -> (A_bar, B_bar, C_bar, S_bar, z_bar), as scvx_hip.unpack_disc."""
         from . import unpack_disc

@@ -134,7 +134,8 @@ class ObstacleRowsSpec:
     records).  They share the node's collision slack and w_coll; the QP kernel is not touched (no slack group of
     its own at w_obs, no chord row inside the QP).  QPSpec.j_max is the total capacity per node: the node-level
     collision rows get j_max - 2 intersample_J - 2 J of it.  Works with or without a CouplingSpec, at any world
-    size (per agent and local: no collective).  Built-in models only.  Build-side option; the reference's Jacobi
+    size (per agent and local: no collective).  Any model with a dense roll-out: the built-in ones and every
+    scvx_hip.rtc.DeviceModel (the samples are its first QPSpec.pos_dim states).  Build-side option; the reference's Jacobi
     driver constrains the nodes only."""
     S: int = 8                  # dense samples per segment
     J: int = 2                  # obstacles kept per (agent, segment)
@@ -284,9 +285,9 @@ class JacobiSCvx:
                             overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
         self._ob = None   # continuous-time obstacle rows (obstacle_rows): settings and buffers
         if obstacle_rows is not None:
-            if not isinstance(spec.model, str):
-                raise NotImplementedError("obstacle_rows: the dense roll-out is compiled for the built-in models only "
-                                          "(no runtime-compiled form)")
+            if not isinstance(spec.model, str) and not callable(getattr(spec.model, "rollout_dense", None)):
+                raise NotImplementedError("obstacle_rows: the model offers no dense roll-out (rollout_dense): a built-in "
+                                          "model name or a scvx_hip.rtc.DeviceModel is needed")
             S, J = int(obstacle_rows.S), int(obstacle_rows.J)
             if not 1 <= S <= 16 or not 1 <= J <= 8:
                 raise ValueError(f"ObstacleRowsSpec: 1 <= S <= 16 and 1 <= J <= 8 required, got {S}, {J}")

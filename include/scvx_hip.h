@@ -33,7 +33,8 @@ extern "C" {
                                   scvx_collision_rows_append_batched) and the obstacle scan
                                   (scvx_obstacle_scan_batched) were added to it without a bump: purely
                                   additive, no existing argument list changed; likewise the split QP launch
-                                  (scvx_qp_dispatch_select, scvx_qp_solve_batched_split) */
+                                  (scvx_qp_dispatch_select, scvx_qp_solve_batched_split) and the dense roll-out
+                                  of a runtime-compiled model (scvx_rtc_rollout_dense_batched) */
 
 #define SCVX_OK 0
 #define SCVX_EINVAL (-1)
@@ -529,11 +530,20 @@ int scvx_jacobi_global_rule(int N, int mode, const int32_t* status, const double
  * RK4 with `sub` steps between consecutive samples (exact for the double and the single integrator).
  *   X [N][K][n], U [N][K][m], sigma [N]  ->  P [N][K-1][S+1][3]  the first pos_dim states, zeros past pos_dim
  *                                            L [N][K-1]          polyline length of those samples
- * Limits: 1 <= S <= 16, 1 <= pos_dim <= 3.  Built-in models only: SCVX_MODEL_RUNTIME returns
- * SCVX_EUNSUPPORTED.  params as scvx_foh_batched.
+ * Limits: K >= 2, N >= 0 (N == 0: SCVX_OK, no launch), 1 <= S <= 16, sub >= 1, 1 <= pos_dim <= min(3, n), no null
+ * buffer; anything else is SCVX_EINVAL.  A model id names a built-in model: SCVX_MODEL_RUNTIME returns
+ * SCVX_EUNSUPPORTED here, a runtime-compiled model has the handle-based form below.  params as scvx_foh_batched.
  */
 int scvx_rollout_dense_batched(int model_id, const double* params, int K, int N, const double* X, const double* U,
                                const double* sigma, int S, int sub, int pos_dim, double* P, double* L, void* stream);
+
+/* scvx_rollout_dense_batched for a runtime-compiled user model (scvx_rtc_model_create): the same kernel body
+ * (csrc/foh_body.hpp rollout_dense_body) on the model's own f, with the same argument rules (n = the model's n_x,
+ * which may be 1 or 2) and the same outputs, so the separation scan, the obstacle scan and the continuous-time rows
+ * built on P / L serve any model.  params / n_params as scvx_rtc_foh_batched.  (added to version 7) */
+int scvx_rtc_rollout_dense_batched(const scvx_rtc_model* model, const double* params, int n_params, int K, int N,
+                                   const double* X, const double* U, const double* sigma, int S, int sub,
+                                   int pos_dim, double* P, double* L, void* stream);
 
 /*
  * Continuous-time closest approach on those samples.  For local agents [i0, i0 + N_local) of P_all

@@ -5,7 +5,10 @@ workloads.synthetic_lattice).  HIP events around each launch, median of 20 launc
 Prints one JSON line per (shape, kernel) with the algorithmic chord-test count N^2 (K-1) S x 25 FLOP and the
 fraction of the 78.6 TFLOP/s FP64 vector peak that count corresponds to (the skip does less than the count, so
 its figure is an equivalent rate, not an achieved one).
-usage: python tools/separation_time.py [S]"""
+--rtc: instead, at the C3 shape only, the dense roll-out of a runtime-compiled model (scvx_hip.rtc.DeviceModel
+re-traced from the drop-in double integrator: scvx_rtc_rollout_dense) against the built-in "di" launch of the same
+process, the two alternating; one JSON line each and the largest difference of their samples.
+usage: python tools/separation_time.py [S] [--rtc]"""
 import json
 import os
 import sys
@@ -40,6 +43,24 @@ def timed(fns):
     return {k: float(np.median(v)) for k, v in ms.items()}
 
 
+def rtc_rollout(S):
+    """The run-time roll-out against the built-in one at the C3 shape."""
+    from scvx_hip.rtc import DeviceModel
+    from SCvx.models.double_integrator_model import DoubleIntegratorModel
+    dev = torch.device("cuda:0")
+    sc = workloads.synthetic_di(1024, K=bench.K, seed=1, sigma=bench.SIGMA, obstacles=bench.N_OBS)
+    X, U, sig = (torch.tensor(sc[k], device=dev) for k in ("X", "U", "sigma"))
+    N, K = X.shape[0], X.shape[1]
+    dm = DeviceModel.from_callables(*DoubleIntegratorModel().get_equations(), 6, 3)
+    a, b = scvx_hip.rollout_dense("di", X, U, sig, S=S), dm.rollout_dense(X, U, sig, S=S, nsub=1, pos_dim=3)
+    t = timed({"rollout_dense": lambda: scvx_hip.rollout_dense("di", X, U, sig, S=S),
+               "rtc_rollout_dense": lambda: dm.rollout_dense(X, U, sig, S=S, nsub=1, pos_dim=3)})
+    for k, ms in t.items():
+        print(json.dumps(dict(shape="c3", N=N, K=K, S=S, kernel=k, median_ms=round(ms, 4))), flush=True)
+    print(json.dumps(dict(shape="c3", max_abs_diff_P=float((a[0] - b[0]).abs().max().item()),
+                          max_abs_diff_L=float((a[1] - b[1]).abs().max().item()))), flush=True)
+
+
 def main(S=8):
     S = int(S)
     dev = torch.device("cuda:0")
@@ -66,4 +87,8 @@ def main(S=8):
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:2])
+    args = [a for a in sys.argv[1:] if a != "--rtc"]
+    if "--rtc" in sys.argv[1:]:
+        rtc_rollout(int(args[0]) if args else 8)
+    else:
+        main(*args[:1])
