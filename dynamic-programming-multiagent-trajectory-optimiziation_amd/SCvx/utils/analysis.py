@@ -148,6 +148,35 @@ def min_agent_obstacle_clearance_continuous(X_list: List[np.ndarray], U_list: Li
     return out["min"], out["D"].cpu().numpy()
 
 
+def min_agent_moving_obstacle_clearance_continuous(X_list: List[np.ndarray], U_list: List[np.ndarray], foh_or_model,
+                                                   sigma, tracks: Sequence, robot_radius: float, S: int = 8,
+                                                   device="cuda", pos_dim=None) -> Tuple[float, np.ndarray]:
+    """min_agent_obstacle_clearance_continuous for obstacles that move (not in the reference): (d_min_global, d_mat)
+    with d_mat[i, j] = min over agent i's whole trajectory, on its own clock, of
+    ||p_i(t) - q_j(t)|| - (robot_radius + r_j); d_min_global its minimum (negative when penetrating).
+
+    tracks [(knots, (t0, t1), radius)]: track j has n >= 1 knots of up to 3 coordinates equally spaced over the
+    real-time window [t0, t1]; it waits at its first knot before t0 and stops at its last after t1; one knot is a
+    fixed centre (scvx_hip.obstacle_tracks).  The other arguments as min_agent_obstacle_clearance_continuous.
+
+    Accuracy: exact for the piecewise-linear interpolant of S relative samples per segment; within
+    max ||p''|| h^2 / 8 of the continuous minimum, h = 1 / ((K-1) S) in normalised time (double integrator:
+    ||p''|| <= max(sigma^2 ||u||)), plus h / 4 times the track's velocity jump (per unit normalised time) for every
+    knot that falls strictly inside a sub-interval (scvx_hip.moving_obstacle_scan)."""
+    import torch
+    who = "min_agent_moving_obstacle_clearance_continuous"
+    model, params, device = _device_model(foh_or_model, device)
+    N = len(X_list)
+    if len(U_list) != N:
+        raise ValueError(f"{who}: X_list and U_list must have the same length")
+    sig = np.broadcast_to(np.asarray(sigma, float), (N,)).copy()
+    K = np.asarray(X_list[0]).shape[1]
+    out = scvx_hip.fleet_moving_obstacle_clearance(model, _stack(X_list, device), _stack(U_list, device),
+                                                   torch.as_tensor(sig, device=device), tracks, robot_radius, S=S,
+                                                   nsub=_rollout_nsub(model, sig, K), pos_dim=pos_dim, params=params)
+    return out["min"], out["D"].cpu().numpy()
+
+
 def min_inter_agent_separation_continuous(X_list: List[np.ndarray], U_list: List[np.ndarray], foh_or_model, sigma,
                                           S: int = 8, device="cuda", pos_dim=None):
     """Closest approach of any two agents in continuous time (not in the reference): (d_min_global, d_seg, info).

@@ -1048,6 +1048,177 @@ def fleet_obstacle_clearance(model, X, U, sigma, obstacles, robot_radius=0.0, S=
     return out
 
 
+class ObstacleTracks(tuple):
+    """(knots (O,M_max,3), n_knots (O,) int32, window (O,2), rho (O,)) device tensors made and validated by
+    obstacle_tracks; passes through it unchanged."""
+    __slots__ = ()
+
+
+def obstacle_tracks(tracks, device):
+    """Moving obstacles [(knots, (t0, t1), rho)] -> ObstacleTracks, the device arrays of moving_obstacle_scan.
+    Track o: n_o >= 1 knots of 1..3 coordinates each (zero-padded like the static centres), equally spaced over the
+    real-time window [t0, t1]; rho the total radius.  One knot: a fixed centre, the window is ignored (None will do).
+    Two or more need t1 > t0: q(t) = c_m + (u - m)(c_{m+1} - c_m) with u = clamp((t - t0) / (t1 - t0), 0, 1) (n - 1),
+    m = min(floor(u), n - 2) -- the obstacle waits at its first knot before t0 and stops at its last after t1; a
+    constant-velocity intruder is two knots.  Validated here, on the host; an ObstacleTracks made before passes
+    through."""
+    import numpy as np
+    torch = _torch()
+    if isinstance(tracks, ObstacleTracks):
+        return tracks
+    tracks = list(tracks)
+    if not tracks:
+        raise ValueError("obstacle_tracks: at least one track required")
+    ks = []
+    for kn, _, _ in tracks:
+        kn = np.asarray(kn, float)
+        kn = kn.reshape(1, -1) if kn.ndim == 1 else kn
+        if kn.ndim != 2 or kn.shape[0] < 1 or not 1 <= kn.shape[1] <= 3 or not np.isfinite(kn).all():
+            raise ValueError("obstacle_tracks: a track's knots must be (n >= 1, 1..3 coordinates), finite")
+        ks.append(kn)
+    O, M = len(ks), max(k.shape[0] for k in ks)
+    knots, win = np.zeros((O, M, 3)), np.zeros((O, 2))
+    win[:, 1] = 1.0
+    for o, (kn, (_, w, _)) in enumerate(zip(ks, tracks)):
+        knots[o, :kn.shape[0], :kn.shape[1]] = kn
+        if kn.shape[0] >= 2:
+            t0, t1 = (float(x) for x in w)
+            if not (np.isfinite(t0) and np.isfinite(t1) and t1 > t0):
+                raise ValueError(f"obstacle_tracks: track {o} has {kn.shape[0]} knots and needs a window t1 > t0, "
+                                 f"got ({t0}, {t1})")
+            win[o] = t0, t1
+    rho = np.array([float(r) for _, _, r in tracks])
+    if not np.isfinite(rho).all():
+        raise ValueError("obstacle_tracks: rho must be finite")
+    return ObstacleTracks((torch.as_tensor(knots, device=device),
+                           torch.as_tensor(np.array([k.shape[0] for k in ks], np.int32), device=device),
+                           torch.as_tensor(win, device=device), torch.as_tensor(rho, device=device)))
+
+
+def moving_obstacle_scan(P, sigma, tracks, cull=None, J=0, analysis=True, node_rows=True, stream=None):
+    """obstacle_scan against obstacles that move (scvx_moving_obstacle_scan_batched).  P (N,K-1,S+1,3) the dense
+    samples of rollout_dense, sigma (N,) the agents' final times: agent i lives on its own clock, sample s of segment
+    k is at t = sigma_i (k S + s) / ((K-1) S).  tracks: [(knots, (t0, t1), rho)] or an ObstacleTracks
+    (obstacle_tracks).  The chords run on the relative samples d_s = p_s - q_o(t_s).  Returns obstacle_scan's dict --
+    dist, alpha (N,K-1,O) with analysis; rec, obs, rec_alpha, count with J in 1..8 (K <= 64; cull None: the largest
+    rho) -- plus, with J >= 1 and node_rows, the node records the QP kernel cannot hold for a centre that moves: per
+    segment's first node (sample 0; node K-1 gets none) the J obstacles of largest v = rho - |d_0| with v > -cull and
+    |d_0| > 0, descending (v, then ascending o): node_rec (N,K-1,J,4) = (d_0 / |d_0|, v), node_obs (N,K-1,J) int32
+    (-1 past the count), node_count (N,K-1) int32; append_node_rows takes them as they are.  With one knot per track
+    every output is obstacle_scan's bit for bit.
+    Accuracy.  The scan is exact for the piecewise-linear interpolant of the relative samples r = p - q.  On a
+    sub-interval of length h = 1 / ((K-1) S) (normalised time) on which r is twice differentiable the interpolant is
+    within max ||r''|| h^2 / 8 of r.  q is piecewise linear: r'' = p'' except at a knot time, where r' jumps by the
+    change dv of the obstacle's velocity (per unit normalised time).  Such a jump at a point a of (0, h) adds the
+    term -dv max(0, t - a) to r, which is farthest from its own chord at t = a: ||dv|| a (h - a) / h <= ||dv|| h / 4.
+    Hence: within max ||p''|| h^2 / 8 + (h / 4) sum ||dv|| of the continuous minimum, the sum over the knots that
+    fall strictly inside one sub-interval (the first and the last knot, where the obstacle starts and stops,
+    included)."""
+    torch = _torch()
+    if P.dim() != 4 or P.shape[3] != 3 or P.shape[2] < 2 or P.shape[1] < 1:
+        raise ValueError("moving_obstacle_scan: P (N,K-1,S+1,3) with K >= 2 and S >= 1 expected")
+    N, Km1, S = P.shape[0], P.shape[1], P.shape[2] - 1
+    J = int(J)
+    if S > 16 or not 0 <= J <= 8 or (J and Km1 >= 64) or not (J or analysis):
+        raise ValueError(f"moving_obstacle_scan: S <= 16 and 0 <= J <= 8 required (records: K <= 64; J = 0 needs "
+                         f"analysis=True); got S={S}, J={J}, K={Km1 + 1}")
+    if tuple(sigma.shape) != (N,):
+        raise ValueError(f"moving_obstacle_scan: sigma ({N},) expected")
+    dev = P.device
+    kd, nd, wd, rd = obstacle_tracks(tracks, dev)
+    if kd.dim() != 3 or kd.shape[2] != 3 or not kd.shape[0] or not kd.shape[1] or tuple(nd.shape) != (kd.shape[0],) \
+            or tuple(wd.shape) != (kd.shape[0], 2) or tuple(rd.shape) != (kd.shape[0],):
+        raise ValueError("moving_obstacle_scan: knots (O,M_max,3), n_knots (O,), window (O,2), rho (O,) expected")
+    O, M = kd.shape[0], kd.shape[1]
+    cull = float(rd.max().item()) if cull is None else float(cull)
+    if J and not cull > 0.0:
+        raise ValueError(f"moving_obstacle_scan: cull > 0 required, got {cull}")
+    out = {}
+    if analysis:
+        out["dist"] = torch.empty((N, Km1, O), dtype=torch.float64, device=dev)
+        out["alpha"] = torch.empty((N, Km1, O), dtype=torch.float64, device=dev)
+    if J:
+        out["rec"] = torch.empty((N, Km1, J, 4), dtype=torch.float64, device=dev)
+        out["obs"] = torch.empty((N, Km1, J), dtype=torch.int32, device=dev)
+        out["rec_alpha"] = torch.empty((N, Km1, J), dtype=torch.float64, device=dev)
+        out["count"] = torch.empty((N, Km1), dtype=torch.int32, device=dev)
+        if node_rows:
+            out["node_rec"] = torch.empty((N, Km1, J, 4), dtype=torch.float64, device=dev)
+            out["node_obs"] = torch.empty((N, Km1, J), dtype=torch.int32, device=dev)
+            out["node_count"] = torch.empty((N, Km1), dtype=torch.int32, device=dev)
+    ptr = lambda k, dt=None: _dev(out[k], dt, k) if k in out else None  # noqa: E731
+    i32 = torch.int32
+    rc = lib().scvx_moving_obstacle_scan_batched(Km1 + 1, S, N, _dev(P, name="P"), _dev(sigma, name="sigma"), O, M,
+                                                 _dev(kd, name="knots"), _dev(nd, i32, "n_knots"),
+                                                 _dev(wd, name="window"), _dev(rd, name="rho"), cull, J, ptr("dist"),
+                                                 ptr("alpha"), ptr("rec"), ptr("obs", i32), ptr("rec_alpha"),
+                                                 ptr("count", i32), ptr("node_rec"), ptr("node_obs", i32),
+                                                 ptr("node_count", i32), _stream(stream))
+    check(rc, "scvx_moving_obstacle_scan_batched")
+    return out
+
+
+def append_node_rows(X_all, i0, node_rec, node_count, rows, count, pos_dim=3, idx=None, overflow=None,
+                     check_index=True, stream=None):
+    """Append the node records of moving_obstacle_scan behind the rows a node already has
+    (scvx_node_rows_append_batched): record r of node_rec[a][t] becomes the row (g, b = v + g . pbar_t) at node t,
+    pbar = X_all (N_total,K,n) the current iterate; none at node K-1.  rows, count, overflow, idx and check_index as
+    append_collision_rows.  Returns (rows, count, overflow)."""
+    torch = _torch()
+    N_total, K, n_x = X_all.shape
+    i0, pos_dim = int(i0), int(pos_dim)
+    if node_rec.dim() != 4 or tuple(node_rec.shape[1:2] + node_rec.shape[3:]) != (K - 1, 4) or \
+            tuple(node_count.shape) != tuple(node_rec.shape[:2]):
+        raise ValueError(f"append_node_rows: node_rec (n,{K - 1},J,4) and node_count (n,{K - 1}) expected")
+    n_rec, J = int(node_rec.shape[0]), int(node_rec.shape[2])
+    n = n_rec if idx is None else int(idx.shape[0])
+    if not 1 <= J <= 8 or not 2 <= K <= 64 or not 1 <= pos_dim <= min(3, n_x) or i0 < 0 or i0 + n_rec > N_total:
+        raise ValueError(f"append_node_rows: 1 <= J <= 8, 2 <= K <= 64, 1 <= pos_dim <= {min(3, n_x)} and "
+                         f"0 <= i0, i0 + n <= N_total required; got J={J}, K={K}, pos_dim={pos_dim}, i0={i0}")
+    if rows.dim() != 4 or rows.shape[0] < n or tuple(rows.shape[1:2] + rows.shape[3:]) != (K, pos_dim + 1) or \
+            count.dim() != 2 or count.shape[0] < n or count.shape[1] != K or not 1 <= rows.shape[2] <= 32:
+        raise ValueError(f"append_node_rows: rows (>= {n},{K},j_max <= 32,{pos_dim + 1}) and count (>= {n},{K}) expected")
+    if idx is not None and check_index and n and (int(idx.min()) < i0 or int(idx.max()) >= i0 + n_rec):
+        raise ValueError("append_node_rows: idx outside the agents [i0, i0 + node_rec.shape[0]) the records cover")
+    if overflow is None:
+        overflow = torch.zeros((1,), dtype=torch.int32, device=X_all.device)
+    rc = lib().scvx_node_rows_append_batched(K, pos_dim, n_x, N_total, _dev(X_all, name="X_all"), i0,
+                                             _dev(idx, torch.int32, "idx") if idx is not None else None, n, J,
+                                             _dev(node_rec, name="node_rec"),
+                                             _dev(node_count, torch.int32, "node_count"), int(rows.shape[2]),
+                                             _dev(rows, name="rows"), _dev(count, torch.int32, "count"),
+                                             _dev(overflow, torch.int32, "overflow"), _stream(stream))
+    check(rc, "scvx_node_rows_append_batched")
+    return rows, count, overflow
+
+
+def fleet_moving_obstacle_clearance(model, X, U, sigma, tracks, robot_radius=0.0, S=8, nsub=None, pos_dim=None,
+                                    params=None, stream=None):
+    """rollout_dense + moving_obstacle_scan of a whole fleet, the counterpart of fleet_obstacle_clearance for
+    obstacles that move: tracks [(knots, (t0, t1), radius r_o)] (obstacle_tracks).  Returns clear (N,K-1,O) =
+    dist - (r_o + robot_radius) per segment, tau (N,K-1,O) where in the segment it occurs, D (N,O) the minimum over
+    the segments, agent_min (N,), min (float) and argmin = (i, o, k, tau), plus P, L (the samples).  model: a built-in
+    name or a DeviceModel (pos_dim required), as rollout_dense; the scan reads only the samples.  Accuracy: that of
+    moving_obstacle_scan -- within max ||p''|| h^2 / 8 plus h / 4 times the obstacle's velocity jump (per unit
+    normalised time, sigma_i times the real one) for every knot strictly inside a sub-interval; for the double
+    integrator ||p''|| <= max(sigma^2 ||u||), and a constant-velocity track whose window covers the horizon has no
+    jump."""
+    torch = _torch()
+    tr = obstacle_tracks(tracks, X.device)
+    P, L = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim, params=params, stream=stream)
+    sc = moving_obstacle_scan(P, sigma, tr, stream=stream)
+    clear = sc["dist"] - (tr[3] + float(robot_radius))
+    out = dict(clear=clear, tau=sc["alpha"], P=P, L=L, D=clear.min(dim=1).values)
+    out["agent_min"] = out["D"].min(dim=1).values
+    O = clear.shape[2]
+    flat = int(clear.argmin().item())
+    i, rest = divmod(flat, clear.shape[1] * O)
+    k, o = divmod(rest, O)
+    out["min"] = float(clear[i, k, o].item())
+    out["argmin"] = (i, o, k, float(sc["alpha"][i, k, o].item()))
+    return out
+
+
 def pair_min_distance(X, rows=None, stream=None):
     """min_inter_agent_distance's matrix (SCvx/utils/analysis.py:10-31) on the device: X (N,K,n) -> D (N,N),
     D[i,j] = min_k ||X[i,k,:rows] - X[j,k,:rows]||, symmetric with a zero diagonal.  rows None: min(3, n), the

@@ -33,7 +33,8 @@ EXPORTS = ("scvx_version", "scvx_last_error", "scvx_foh_batched", "scvx_integrat
            "scvx_jacobi_update_costs_batched", "scvx_jacobi_global_rule", "scvx_rollout_dense_batched",
            "scvx_separation_scan_batched", "scvx_pair_min_distance_batched", "scvx_obstacle_min_distance_batched",
            "scvx_intersample_pair_rows_batched", "scvx_collision_rows_append_batched", "scvx_obstacle_scan_batched",
-           "scvx_qp_dispatch_select", "scvx_qp_solve_batched_split", "scvx_rtc_rollout_dense_batched")
+           "scvx_qp_dispatch_select", "scvx_qp_solve_batched_split", "scvx_rtc_rollout_dense_batched",
+           "scvx_moving_obstacle_scan_batched", "scvx_node_rows_append_batched")
 SCVX_MAX_MODEL_PARAMS, SCVX_RTC_MAX_NX, SCVX_RTC_MAX_NU = 16, 16, 8
 
 
@@ -164,6 +165,13 @@ def lib():
             raise ImportError(f"{LIB_PATH} lacks the user models' dense roll-out entry point: rebuild it "
                               f"(`make -C {os.path.dirname(HERE)}`)")
         L.scvx_rtc_rollout_dense_batched.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+        if not hasattr(L, "scvx_moving_obstacle_scan_batched"):
+            raise ImportError(f"{LIB_PATH} lacks the moving-obstacle entry points: rebuild it "
+                              f"(`make -C {os.path.dirname(HERE)}`)")
+        L.scvx_moving_obstacle_scan_batched.argtypes = ([i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, dbl, i32]
+                                                        + [vp] * 10)
+        L.scvx_node_rows_append_batched.argtypes = [i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp,
+                                                    vp]
         sized = ("scvx_last_error", "scvx_qp_workspace_bytes", "scvx_scp_workspace_bytes", "scvx_rtc_model_source",
                  "scvx_rtc_model_log")
         for fn in EXPORTS:

@@ -16,9 +16,10 @@ import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
-from . import (QPSolver, QPSpec, append_collision_rows, collision_check, collision_rows, collision_rows_indexed,
-               default_nsub, fleet_obstacle_clearance, fleet_separation, foh_batched, intersample_pair_rows,
-               jacobi_update, jacobi_update_global, model_dims, obstacle_scan, rollout_dense)
+from . import (ObstacleTracks, QPSolver, QPSpec, append_collision_rows, append_node_rows, collision_check, collision_rows,
+               collision_rows_indexed, default_nsub, fleet_moving_obstacle_clearance, fleet_obstacle_clearance,
+               fleet_separation, foh_batched, intersample_pair_rows, jacobi_update, jacobi_update_global, model_dims,
+               moving_obstacle_scan, obstacle_scan, obstacle_tracks, rollout_dense)
 
 # The split QP launch of JacobiSCvx (dispatch_order="lpt", every agent resident): the measured settings of
 # profiles/split_sweep.txt (DESIGN §3.3 "Split launch").  SPLIT_DEFAULT: what an unset SCVX_QP_SPLIT stands for ("1": on
@@ -78,6 +79,7 @@ class HipBackend:
         obstacles' device arrays are made once per list object."""
         if P is None:
             P, _ = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim)
+            self.samples = (S, P)   # for moving_obstacle_rows of the same step
         cached = getattr(self, "_obs_dev", None)
         if cached is None or cached[0] is not obstacles or cached[1][0].device != X.device:
             from . import _obstacle_arrays
@@ -85,9 +87,25 @@ class HipBackend:
         out = obstacle_scan(P, cached[1], cull=cull, J=J, analysis=False)
         return out["rec"], out["count"]
 
+    def moving_obstacle_rows(self, model, X, U, sigma, S, nsub, pos_dim, tracks, cull, J, P=None):
+        """(rec, count_seg, node_rec, node_count) of the moving-obstacle rows of every agent of the iterate (X, U) on
+        this rank's own clocks sigma: the dense roll-out (P: as obstacle_rows), then the moving-obstacle scan.  The
+        tracks' device arrays are made once per list object."""
+        if P is None:
+            P, _ = rollout_dense(model, X, U, sigma, S=S, nsub=nsub, pos_dim=pos_dim)
+        cached = getattr(self, "_trk_dev", None)
+        if cached is None or cached[0] is not tracks or cached[1][0].device != X.device:
+            cached = self._trk_dev = (tracks, obstacle_tracks(tracks, X.device))
+        out = moving_obstacle_scan(P, sigma, cached[1], cull=cull, J=J, analysis=False)
+        return out["rec"], out["count"], out["node_rec"], out["node_count"]
+
     def append_collision_rows(self, X_all, i0, idx, rec, count_seg, rows, count, pos_dim, overflow):
         return append_collision_rows(X_all, i0, rec, count_seg, rows, count, pos_dim, idx=idx, overflow=overflow,
                                      check_index=False)   # idx comes from this rank's own agents
+
+    def append_node_rows(self, X_all, i0, idx, node_rec, node_count, rows, count, pos_dim, overflow):
+        return append_node_rows(X_all, i0, node_rec, node_count, rows, count, pos_dim, idx=idx, overflow=overflow,
+                                check_index=False)
 
     def qp_solver(self, spec, N, device):
         return QPSolver(spec, N, device=device)
@@ -143,6 +161,26 @@ class ObstacleRowsSpec:
     obstacles: Optional[Sequence] = None   # [(centre, total radius rho)]; None: QPSpec.obs, the node rows' list
 
 
+@dataclass
+class MovingObstaclesSpec:
+    """Moving obstacles, JacobiSCvx(..., moving_obstacles=MovingObstaclesSpec(tracks)): things that move
+    along a known track and are not ours to plan.  tracks: [(knots, (t0, t1), total radius rho)]
+    (scvx_hip.obstacle_tracks), in real time; every agent meets them on its own clock sigma_i.  Every step rolls the
+    iterate out with S samples per segment and scans the relative samples p - q_o(t): per node t < K-1 the J tracks
+    closest to their surface at the node (within cull of it) give one node row each -- the QP kernel holds node rows
+    for fixed centres only -- and per segment the J tracks that come closest strictly between two nodes give two node
+    rows each, as the static obstacle records do.  Per node they follow whatever rows the node already has: collision
+    node rows, pair records, static obstacle records, then the moving node rows, then the moving segment records.
+    They take 3 J of QPSpec.j_max per node (J node rows, 2 J from the two adjoining segments), share the node's
+    collision slack and w_coll, and leave the QP kernel untouched.  Works with or without a CouplingSpec and
+    obstacle_rows, at any world size (per agent and local: this rank's sigma, no collective), for any model with a
+    dense roll-out."""
+    tracks: Sequence            # [(knots, (t0, t1), rho)], at least one
+    S: int = 8                  # dense samples per segment
+    J: int = 2                  # tracks kept per node and per (agent, segment)
+    cull: float = 0.0           # tracks whose surface stays farther than this give no row; <= 0: the largest rho
+
+
 class JacobiSCvx:
     """Device-resident Jacobi SCvx for this rank's agents [i0, i0 + N_local) of N_total.
 
@@ -187,6 +225,8 @@ class JacobiSCvx:
     obstacle_rows: an ObstacleRowsSpec adds continuous-time obstacle rows to every subproblem (see there); None
              (default): off, nothing changes.  The rows share the node's collision slack and w_coll; the QP kernel is
              not touched.
+    moving_obstacles: a MovingObstaclesSpec adds node rows and continuous-time rows against obstacles that move along
+             known tracks (see there); None (default): off, nothing changes.
     """
 
     def __init__(self, spec: QPSpec, x_init, x_final, sigma, tr0: float, coupling: Optional[CouplingSpec] = None,
@@ -195,7 +235,8 @@ class JacobiSCvx:
                  tie_rtol: float = 1e-9, warm_start: bool = True, warm_max_status: int = 0,
                  dispatch_order: str = "lpt", obstacle_rows: Optional["ObstacleRowsSpec"] = None,
                  split_thr: Optional[int] = None, split_T: Optional[int] = None,
-                 split_reserve: Optional[str] = None, split_short_per_tail: Optional[int] = None):
+                 split_reserve: Optional[str] = None, split_short_per_tail: Optional[int] = None,
+                 moving_obstacles: Optional["MovingObstaclesSpec"] = None):
         import torch
         self.torch = torch
         self.backend = backend or HipBackend()
@@ -279,7 +320,7 @@ class JacobiSCvx:
                                  f"per node and must leave at least one node-level row next to the 2 x intersample_J = "
                                  f"{2 * J} continuous-time rows")
             cull = float(coupling.intersample_cull) if coupling.intersample_cull > 0 else 3.0 * coupling.R
-            self._is = dict(S=S, J=J, cull=cull, j_node=j_node, rec=None, count_seg=None,
+            self._is = dict(S=S, J=J, per_node=2 * J, cull=cull, j_node=j_node, rec=None, count_seg=None,
                             rows_node=torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
                                                   device=self.device),
                             overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
@@ -302,8 +343,8 @@ class JacobiSCvx:
                                  + (f", the 2 x intersample_J = {2 * J_pair} pair rows" if J_pair else "")
                                  + (" and at least one node-level row" if coupling is not None else ""))
             cull = float(obstacle_rows.cull) if obstacle_rows.cull > 0 else max(float(r) for _, r in obstacles)
-            self._ob = dict(S=S, J=J, cull=cull, obstacles=obstacles, j_node=j_node, rec=None, count_seg=None,
-                            overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
+            self._ob = dict(S=S, J=J, per_node=2 * J, cull=cull, obstacles=obstacles, j_node=j_node, rec=None,
+                            count_seg=None, overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
             if coupling is None:   # independent agents: the driver owns the rows, all of them obstacle rows
                 self.rows = torch.zeros((self.N, spec.K, spec.j_max, spec.pos_dim + 1), dtype=torch.float64,
                                         device=self.device)
@@ -314,6 +355,47 @@ class JacobiSCvx:
             else:
                 self._ob["rows_node"] = torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
                                                     device=self.device)
+        self._mv = None   # moving obstacles (moving_obstacles): settings and buffers
+        if moving_obstacles is not None:
+            if not isinstance(spec.model, str) and not callable(getattr(spec.model, "rollout_dense", None)):
+                raise NotImplementedError("moving_obstacles: the model offers no dense roll-out (rollout_dense): a "
+                                          "built-in model name or a scvx_hip.rtc.DeviceModel is needed")
+            S, J = int(moving_obstacles.S), int(moving_obstacles.J)
+            if not 1 <= S <= 16 or not 1 <= J <= 8:
+                raise ValueError(f"MovingObstaclesSpec: 1 <= S <= 16 and 1 <= J <= 8 required, got {S}, {J}")
+            if spec.K > 64:
+                raise ValueError(f"MovingObstaclesSpec: K <= 64 required (the records' limit), got {spec.K}")
+            tracks = moving_obstacles.tracks
+            if not isinstance(tracks, ObstacleTracks):
+                tracks = list(tracks)
+                if not tracks:
+                    raise ValueError("MovingObstaclesSpec: no tracks")
+            rmax = float(obstacle_tracks(tracks, "cpu")[3].max().item())   # (a list is validated here, on the host)
+            earlier = self._records()
+            j_node = spec.j_max - sum(s["per_node"] for s in earlier) - 3 * J
+            if j_node < (1 if coupling is not None else 0):
+                raise ValueError(f"moving_obstacles: QPSpec.j_max = {spec.j_max} is the total capacity per node and "
+                                 f"must hold the 3 x J = {3 * J} moving-obstacle rows (J node rows, 2 J from the two "
+                                 f"adjoining segments)"
+                                 + "".join(f", the {s['per_node']} {n} rows" for s, n in
+                                           ((self._is, "pair"), (self._ob, "obstacle")) if s is not None)
+                                 + (" and at least one node-level row" if coupling is not None else ""))
+            cull = float(moving_obstacles.cull) if moving_obstacles.cull > 0 else rmax
+            self._mv = dict(S=S, J=J, per_node=3 * J, cull=cull, tracks=tracks, j_node=j_node, rec=None, count_seg=None,
+                            node_rec=None, node_count=None,
+                            overflow=torch.zeros((1,), dtype=torch.int32, device=self.device))
+            for s in earlier:   # the node-level share shrinks for every set
+                s["j_node"] = j_node
+                if "rows_node" in s:
+                    s["rows_node"] = s["rows_node"][:, :, :j_node].contiguous()
+            if coupling is None:
+                if not earlier:   # independent agents: the driver owns the rows, none of them node-level
+                    self.rows = torch.zeros((self.N, spec.K, spec.j_max, spec.pos_dim + 1), dtype=torch.float64,
+                                            device=self.device)
+                    self.count = torch.zeros((self.N, spec.K), dtype=torch.int32, device=self.device)
+            elif not earlier:
+                self._mv["rows_node"] = torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
+                                                    device=self.device)
 
     def _cu_count(self):
         """Compute units of this driver's GPU (0: no GPU -- stub backends; every dispatch option is then off)"""
@@ -322,8 +404,18 @@ class JacobiSCvx:
         return int(self.torch.cuda.get_device_properties(self.device).multi_processor_count)
 
     def _records(self):
-        """The record sets appended behind the node rows, in order: pair records, then obstacle records."""
-        return [s for s in (self._is, self._ob) if s is not None]
+        """The record sets appended behind the node rows, in order: pair records, static obstacle records, moving
+        obstacles.  Each states the rows it may add to a node (per_node) and is appended by _append."""
+        return [s for s in (self._is, self._ob, self._mv) if s is not None]
+
+    def _append(self, s, X_all, i0, idx, rows, count):
+        """The appends of record set s behind the count rows of every node: a moving-obstacle set's node rows first
+        (one row per record), then a set's segment records (two rows per record).  idx: the re-solve's agents."""
+        if s.get("node_rec") is not None:
+            self.backend.append_node_rows(X_all, i0, idx, s["node_rec"], s["node_count"], rows, count,
+                                          self.spec.pos_dim, s["overflow"])
+        return self.backend.append_collision_rows(X_all, i0, idx, s["rec"], s["count_seg"], rows, count,
+                                                  self.spec.pos_dim, s["overflow"])
 
     def _hi_buffers(self):
         """Rows, counts and a QPSolver at j_max_hi sized for all N local agents, allocated once: a re-solve
@@ -336,7 +428,7 @@ class JacobiSCvx:
                             count=torch.zeros((self.N, spec.K), dtype=torch.int32, device=self.device),
                             solver=self.backend.qp_solver(spec_hi, self.N, self.device))
             if self._records():   # the node-level share of j_max_hi, before the continuous-time rows join it
-                j_node = c.j_max_hi - 2 * sum(s["J"] for s in self._records())
+                j_node = c.j_max_hi - sum(s["per_node"] for s in self._records())
                 self._hi["rows_node"] = torch.zeros((self.N, spec.K, j_node, spec.pos_dim + 1), dtype=torch.float64,
                                                     device=self.device)
         return self._hi
@@ -364,14 +456,13 @@ class JacobiSCvx:
         if not self._records():
             self.backend.collision_rows_indexed(X_all, gidx, c.R, c.j_max_hi, spec.pos_dim, c.cull_radius, hi["rows"],
                                                 hi["count"])
-        else:   # j_max_hi - 2 (J_pair + J_obs) node rows, then the step's own continuous-time records of those agents
-            j_node = c.j_max_hi - 2 * sum(s["J"] for s in self._records())
+        else:   # j_max_hi less every set's rows per node, then the step's own records of those agents, set by set
+            j_node = c.j_max_hi - sum(s["per_node"] for s in self._records())
             self.backend.collision_rows_indexed(X_all, gidx, c.R, j_node, spec.pos_dim, c.cull_radius,
                                                 hi["rows_node"], hi["count"])
             hi["rows"][:n_bad, :, :j_node].copy_(hi["rows_node"][:n_bad])
             for s in self._records():
-                self.backend.append_collision_rows(X_all, self.i0, gidx, s["rec"], s["count_seg"], hi["rows"],
-                                                   hi["count"], spec.pos_dim, s["overflow"])
+                self._append(s, X_all, self.i0, gidx, hi["rows"], hi["count"])
         g = lambda t: t.index_select(0, idx).contiguous()  # noqa: E731
         o2 = hi["solver"].solve(g(self.disc), g(self.sigma), g(X), g(U), g(self.x_init), g(self.x_final), g(self.tr),
                                 hi["rows"][:n_bad], hi["count"][:n_bad], n=n_bad)
@@ -411,6 +502,15 @@ class JacobiSCvx:
         return fleet_obstacle_clearance(self.spec.model, X, U, self.sigma, obstacles, 0.0, S=S, nsub=self.nsub,
                                         pos_dim=self.spec.pos_dim)
 
+    def moving_obstacle_clearance(self, X, U, S=8):
+        """Continuous-time clearance of every agent to every moving obstacle of the moving_obstacles option at the
+        iterate (X, U), each agent on its own clock (scvx_hip.fleet_moving_obstacle_clearance: S samples per segment,
+        the FOH's substep count, the template's pos_dim; the radii are total radii).  Per agent and local: any world."""
+        if self._mv is None:
+            raise ValueError("JacobiSCvx.moving_obstacle_clearance needs the moving_obstacles option (its tracks)")
+        return fleet_moving_obstacle_clearance(self.spec.model, X, U, self.sigma, self._mv["tracks"], 0.0, S=S,
+                                               nsub=self.nsub, pos_dim=self.spec.pos_dim)
+
     def _mark(self, marks, name):
         """Record a timing event named `name` on the current (launch) stream (marks: list or None)."""
         if marks is not None:
@@ -423,7 +523,8 @@ class JacobiSCvx:
         marks: optional list; (stage, event) pairs are appended on the launch stream -- "start", then
         the end of "foh", "gather" (all-gather), "rows" (collision rows), "isrows" (with CouplingSpec.intersample_S > 0: dense
         roll-out, pair-rows scan and append), "obsrows" (with obstacle_rows: dense roll-out unless shared, obstacle scan and
-        append), "qp" (the QP kernel),
+        append), "movrows" (with moving_obstacles: dense roll-out unless shared, moving-obstacle scan, node-row and record
+        appends), "qp" (the QP kernel),
         "check" (full-row check + re-solve) and "update" (bookkeeping); a stage's time is the
         difference to the previous mark."""
         torch = self.torch
@@ -458,26 +559,39 @@ class JacobiSCvx:
                 s["rec"], s["count_seg"] = self.backend.intersample_pair_rows(
                     spec.model, X, U, self.sigma, s["S"], self.nsub, spec.pos_dim, self.coupling.R, s["cull"], s["J"])
                 s["overflow"].zero_()
-                rows, count, _ = self.backend.append_collision_rows(X_all, self.i0, None, s["rec"], s["count_seg"],
-                                                                    self.rows, self.count, spec.pos_dim, s["overflow"])
+                rows, count, _ = self._append(s, X_all, self.i0, None, self.rows, self.count)
                 self._mark(marks, "isrows")
+        # the dense samples of this iterate, by sample count: a set's roll-out serves the later sets of the step
+        have = {}
+
+        def take_samples():
+            made = getattr(self.backend, "samples", None)
+            if made is not None:
+                have[made[0]] = made[1]
+                self.backend.samples = None
+
+        take_samples()
+        i0_rows = self.i0 if self.coupling is not None else 0
+        if self.coupling is None and self._records():   # independent agents: no node rows, the iterate is its own X_all
+            self.count.zero_()
+            X_all = X if X.is_contiguous() else X.contiguous()
         if self._ob is not None:
             s = self._ob
-            # the pair rows' samples of this iterate serve again when the sample counts agree
-            shared = getattr(self.backend, "samples", None) if self._is is not None else None
-            share = {"P": shared[1]} if shared is not None and shared[0] == s["S"] else {}
-            if shared is not None:
-                self.backend.samples = None
+            share = {"P": have[s["S"]]} if s["S"] in have else {}
             s["rec"], s["count_seg"] = self.backend.obstacle_rows(
                 spec.model, X, U, self.sigma, s["S"], self.nsub, spec.pos_dim, s["obstacles"], s["cull"], s["J"], **share)
+            take_samples()
             s["overflow"].zero_()
-            if self.coupling is None:   # independent agents: no node rows, the iterate is its own X_all
-                self.count.zero_()
-                X_all = X if X.is_contiguous() else X.contiguous()
-            rows, count, _ = self.backend.append_collision_rows(X_all, self.i0 if self.coupling is not None else 0,
-                                                                None, s["rec"], s["count_seg"], self.rows, self.count,
-                                                                spec.pos_dim, s["overflow"])
+            rows, count, _ = self._append(s, X_all, i0_rows, None, self.rows, self.count)
             self._mark(marks, "obsrows")
+        if self._mv is not None:
+            s = self._mv
+            share = {"P": have[s["S"]]} if s["S"] in have else {}
+            s["rec"], s["count_seg"], s["node_rec"], s["node_count"] = self.backend.moving_obstacle_rows(
+                spec.model, X, U, self.sigma, s["S"], self.nsub, spec.pos_dim, s["tracks"], s["cull"], s["J"], **share)
+            s["overflow"].zero_()
+            rows, count, _ = self._append(s, X_all, i0_rows, None, self.rows, self.count)
+            self._mark(marks, "movrows")
         kw = {"order": self.order} if self.order is not None else {}
         if self.order_tail is not None:
             kw.update(order_tail=self.order_tail, reserve=self.split_reserve)
@@ -504,6 +618,8 @@ class JacobiSCvx:
                 self.last_check["is_overflow"] = int(self._is["overflow"].item())
             if self._ob is not None:   # the same for the obstacle rows
                 self.last_check["obs_overflow"] = int(self._ob["overflow"].item())
+            if self._mv is not None:   # and for the moving obstacles' rows
+                self.last_check["mov_overflow"] = int(self._mv["overflow"].item())
             self._mark(marks, "check")
         # an agent whose subproblem failed numerically (status 2) rejects the step: it keeps its
         # iterate (its output may be non-finite and would otherwise reach every other agent through

@@ -34,7 +34,8 @@ extern "C" {
                                   (scvx_obstacle_scan_batched) were added to it without a bump: purely
                                   additive, no existing argument list changed; likewise the split QP launch
                                   (scvx_qp_dispatch_select, scvx_qp_solve_batched_split) and the dense roll-out
-                                  of a runtime-compiled model (scvx_rtc_rollout_dense_batched) */
+                                  of a runtime-compiled model (scvx_rtc_rollout_dense_batched) and the moving
+                                  obstacles (scvx_moving_obstacle_scan_batched, scvx_node_rows_append_batched) */
 
 #define SCVX_OK 0
 #define SCVX_EINVAL (-1)
@@ -644,6 +645,53 @@ int scvx_collision_rows_append_batched(int K, int pos_dim, int n_x, int N_total,
 int scvx_obstacle_scan_batched(int K, int S, int N, const double* P, int O, const double* centers, const double* rho,
                                double cull, int J, double* dist, double* alpha, double* rec, int32_t* obs,
                                double* rec_alpha, int32_t* count, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Moving obstacles: tracked centres in the clearance scan and the QP rows (csrc/moving_obstacles.hip,
+ * DESIGN §3.9).  Two entry points added to revision 7; no existing argument list changed.
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * scvx_obstacle_scan_batched against centres that move.  Track o (device arrays): n_knots[o] in 1..M_max knots
+ * knots [O][M_max][3] (zero-padded past the position dimension, entries past n_knots[o] unread), equally spaced
+ * over the real-time window window [O][2] = (t0, t1), t1 > t0; total radius rho [O].  Its position is
+ *     one knot:   q_o(t) = c_0 (the window is not read)
+ *     otherwise:  u = clamp((t - t0) w, 0, n - 1), w = (n - 1) / (t1 - t0), m = min(floor(u), n - 2),
+ *                 q_o(t) = c_m + (u - m)(c_{m+1} - c_m):  at rest at c_0 before t0 and at c_{n-1} after t1.
+ * The caller guarantees n_knots and the window rule (the entry point reads no device memory; the kernel clamps
+ * n_knots into 1..M_max so that nothing outside the arrays is read).  Agent i lives on its own clock: sample s of
+ * segment k of P [N][K-1][S+1][3] is at t = sigma[i] (k S + s) / ((K-1) S), formed as (sigma[i] / ((K-1) S)) (k S + s).
+ * Obstacle o's closest approach on a segment is the chord formula of scvx_obstacle_scan_batched on the relative
+ * samples d_s = p_s - q_o(t_s): exact for the piecewise-linear interpolant of the relative samples.  With one knot
+ * per obstacle every output is scvx_obstacle_scan_batched's bit for bit.
+ * Analysis outputs (both or neither):   dist [N][K-1][O], alpha [N][K-1][O] = alpha'.
+ * Segment records (all four or none): scvx_obstacle_scan_batched's rec, obs, rec_alpha, count under its rule
+ *     v = rho_o - dist > -cull,   0 < alpha' < 1,   dist > 0;   the J of largest v, descending (v, then ascending o).
+ * Node records (all three or none), which the QP kernel cannot hold for a centre that moves: for the segment's first
+ * node (sample 0; node K-1 gets none) the J obstacles of largest v = rho_o - ||d_0|| with v > -cull and
+ * ||d_0|| > 0, in the same order:
+ *     node_rec [N][K-1][J][4] = (d_0 / ||d_0||, v)   node_obs [N][K-1][J] int32 o   node_count [N][K-1] int32
+ * (slots past the count hold zeros, obs -1).  J >= 1 exactly when segment or node records are asked for.  Every
+ * (agent, segment) is computed on its own: a slice of P and sigma returns the matching rows bit for bit.
+ * Limits: K >= 2, 1 <= S <= 16, O >= 1, M_max >= 1, 0 <= J <= 8; with records K <= 64 and cull > 0.
+ */
+int scvx_moving_obstacle_scan_batched(int K, int S, int N, const double* P, const double* sigma, int O, int M_max,
+                                      const double* knots, const int32_t* n_knots, const double* window,
+                                      const double* rho, double cull, int J, double* dist, double* alpha, double* rec,
+                                      int32_t* obs, double* rec_alpha, int32_t* count, double* node_rec,
+                                      int32_t* node_obs, int32_t* node_count, void* stream);
+
+/*
+ * Append those node records: for local agent a and node t < K-1, behind the count[a][t] rows already present, record
+ * r of node_rec[.][t] becomes the row g'(p_t - pbar_t) >= v - S_t, i.e. (g, b = v + g' pbar_t), pbar_t =
+ * X_all[i][t][0:pos_dim] (summed left to right, unfused).  No row at node K-1.  Arguments, idx form, j_max and
+ * *overflow as scvx_collision_rows_append_batched.
+ *   rows [N_local][K][j_max][pos_dim+1], count [N_local][K] (in / out), node_rec [.][K-1][J][4], node_count [.][K-1].
+ */
+int scvx_node_rows_append_batched(int K, int pos_dim, int n_x, int N_total, const double* X_all, int i0,
+                                  const int32_t* idx, int N_local, int J, const double* node_rec,
+                                  const int32_t* node_count, int j_max, double* rows, int32_t* count,
+                                  int32_t* overflow, void* stream);
 
 #ifdef __cplusplus
 }
